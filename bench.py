@@ -14,8 +14,14 @@ accepted 3D points themselves -- packed on the device (one launch, no host
 sync) and all-gathered over RCCL on a second stream, overlapping the next
 sweep (parallel.PointsExchange).
 
-Beside the headline (rank 0 at N = 1 only, so that the driver's N > 1 runs
-stay short):
+A plain run sets up, warms up, times the --steps sweeps and prints the result
+line; --dump-outputs DIR also writes what the last timed sweep computed (the
+arrays a caller of the scorer receives) as DIR/<name>.npy.
+
+With --full, beside the headline (exchange and roofline on every rank, the
+rest on rank 0 at N = 1 only, so that N > 1 runs stay short):
+  exchange     the per-sweep exchange's payload, its device pack time and the
+               overlap proxy; scaling_baseline: the N = 1 step with the pack
   roofline     the binding roof of the dominant kernel (k_score_mma) from the
                live kernel time and the per-launch counters of the committed
                rocprofv3 PMC profile (profiles/r05/pmc.json): HBM bytes,
@@ -33,7 +39,7 @@ stay short):
                and beside it the reference's own single-core Python rate recorded
                at fixture generation (tests/golden/reference_timing.json)
 
-python bench.py [--gpus N --steps K --warmup W --n CANDS --wid 5]
+python bench.py [--gpus N --steps K --warmup W --n CANDS --wid 5] [--full] [--dump-outputs DIR]
 N > 1: either under a launcher (python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ..., which must start exactly N ranks), or `python bench.py
 --gpus N` alone: the process then starts the N ranks itself as children of a
@@ -148,6 +154,38 @@ def host_outputs(sw, m=None):
         r = sw["rec"][:m].cpu().numpy().view(np.uint64)[:, :-1]
         return r, np.bitwise_count(r).sum(axis=1).astype(np.int32)
     return sw["mask"][:m].cpu().numpy().view(np.uint64), sw["count"][:m].cpu().numpy()
+
+
+DUMP_BYTES = 60 * 1000 * 1000     # --dump-outputs: all arrays together stay below 64 MB
+
+
+def dump_outputs(path, sw):
+    """--dump-outputs: what the last timed sweep gave its caller, as float64
+    arrays path/<name>.npy: xy (n, 2), the projections into the reference view;
+    mask (n, 2 words), the passing views' bits as the low and the high 32 bits
+    of each 64-bit mask word (exact in binary64); count (n,), |V|; avg (n,),
+    the average NCC.  When the rows of n candidates exceed DUMP_BYTES, a fixed
+    sample of them (numpy's default_rng(0), sorted) and its indices as index."""
+    n = sw["n"]
+    if sw["rec"] is not None:
+        r = sw["rec"] if sw.get("last_rec") is None else sw["last_rec"]
+        r = r.cpu().numpy()
+        mask, avg = r[:, :-1].view(np.uint64), r[:, -1].copy().view(np.float64)
+        count = np.bitwise_count(mask).sum(axis=1)
+    else:
+        mask = sw["mask"].cpu().numpy().view(np.uint64)
+        count, avg = sw["count"].cpu().numpy(), sw["avg"].cpu().numpy()
+    arrays = {"xy": sw["xy"].cpu().numpy(),
+              "mask": np.stack([mask & np.uint64(0xFFFFFFFF), mask >> np.uint64(32)], axis=-1).reshape(n, -1),
+              "count": count, "avg": avg}
+    row = 8 * (2 + arrays["mask"].shape[1] + 2 + 1)        # + 1: the index column of a sample
+    if n * row > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // row, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["index"] = idx
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def load_scene():
@@ -399,6 +437,11 @@ def main():
                     help="one queue of --n candidates split over the ranks (default: --n per rank)")
     ap.add_argument("--wid", type=int, default=5)
     ap.add_argument("--thr", type=float, default=0.7)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: exchange and roofline figures, the N = 1 step with the "
+                         "pack, cold sweep, secondary wid, stage, ring256 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed sweep's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=500000,
                     help="candidates the single-threaded oracle scores (~10 s)")
@@ -423,6 +466,8 @@ def main():
     a = ap.parse_args(argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if a.pack_on_comm and a.soa:
         # the SoA outputs are single-buffered: the next sweep would overwrite
         # count / mask while the comm stream's pack still reads them
@@ -499,7 +544,7 @@ def main():
         """steps timed sweeps on stream st (default: the scoring stream) ->
         (wall s (max over ranks), kernel ms per launch, score-call ms, records
         exchanged in the last step)."""
-        got = {"n": 0}
+        got = {"n": 0, "rec": None}
         st = st or stream
         ex = sw.get("exch") if exchange else None
 
@@ -520,6 +565,7 @@ def main():
             if rebuild:
                 cx.rebuild(stream=st.cuda_stream)
             score(cx, sw, wid, a.thr, st, rec)
+            got["rec"] = rec
             if evs is not None:
                 evs[1].record(st)
             if ex is not None:
@@ -557,6 +603,7 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        sw["last_rec"] = got["rec"]          # the buffer the last step scored into (None: sw["rec"])
         return dt, kt / kl, pms, got["n"]
 
     sw = sweep_inputs(V, K, R, t, W, H, a.n, a.strong)
@@ -568,7 +615,7 @@ def main():
     # CU, and the pack + all-gather on the exchange's stream, where they find
     # the free CUs instead of queueing behind the persistent scorer
     mstream, kept, cstream, cowner, owners = stream, None, None, None, []
-    if a.comm_cus > 0 and (world > 1 or rank == 0):
+    if a.comm_cus > 0 and (world > 1 or (rank == 0 and a.full)):
         if a.comm_layout == "mask":
             # the streams' owners (parallel.MaskedStream): closed at the end,
             # or at exit by their atexit hook
@@ -599,6 +646,8 @@ def main():
     dt, kms, pms, gathered = timed(ctx, sw, a.wid, a.steps, a.warmup, st=mstream if world > 1 else stream)
     direct = direct_path(st0, scorer_stats(ctx))
     masked(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, sw)
     value = total_n * a.steps / dt
     accepted = int((host_outputs(sw)[1] >= vlb).sum())
     acc_ranks = [accepted]
@@ -606,7 +655,7 @@ def main():
         acc_ranks = [None] * world
         dist.all_gather_object(acc_ranks, accepted)
     kernel_name = ctx.timed_kernel()
-    solo = rank == 0 and world == 1
+    solo = rank == 0 and world == 1 and a.full
     scaling_base = None
     if solo:
         # the N = 1 step with the N > 1 step's device work minus the gather:
@@ -673,10 +722,12 @@ def main():
         "accepted_per_sweep": accepted,
         "gathered_records": gathered,
         "direct_path": direct,
-        "exchange": exchange_figures(ctx, sw, V, vlb, accepted, world, stream, a.thr, a.wid),
+        "full": a.full,
     }
-    out["roofline"] = roofline(pmc_entry(a.scene, V, a.wid, n, kernel_name), V, a.wid, n, kms, kernel_name,
-                               floor_bytes(rgb, sw["xy"], sw["ref"], a.wid, n))
+    if a.full:
+        out["exchange"] = exchange_figures(ctx, sw, V, vlb, accepted, world, stream, a.thr, a.wid)
+        out["roofline"] = roofline(pmc_entry(a.scene, V, a.wid, n, kernel_name), V, a.wid, n, kms, kernel_name,
+                                   floor_bytes(rgb, sw["xy"], sw["ref"], a.wid, n))
     if solo and not a.no_overlap:
         # the multi-GPU layout: scoring on the CU-masked stream, the pack and
         # the proxy of RCCL's all-gather on the CUs it leaves out

@@ -13,7 +13,7 @@ if [ -z "$NO_TESTS" ]; then
   rc=$?; tail -2 gpurun_out/${T}_pytest.log
   if [ $rc -ne 0 ]; then grep -B5 -A40 "FAILED\|Error" gpurun_out/${T}_pytest.log | head -80; exit $rc; fi
 fi
-B="--no-stage --no-ring --secondary-wid ${SWID:-0} --steps 100 --no-cpu-baseline --no-overlap ${BENCH_ARGS}"
+B="--full --no-stage --no-ring --secondary-wid ${SWID:-0} --steps 100 --no-cpu-baseline --no-overlap ${BENCH_ARGS}"
 L0=$PWD/simple-implementation-of-structure-from-motion-and-multi-view-stereo-by-python_amd/libmvs_amd.so
 for rep in $(seq 1 ${REPS:-2}); do
   for v in main ${VARIANTS}; do

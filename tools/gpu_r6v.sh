@@ -11,7 +11,7 @@ done
 grep mode gpurun_out/r6v_probe.log
 timeout -k 10 300 python -u -m pytest tests/test_gpu_streams.py -x -v --timeout 120 --timeout-method thread -k paired > gpurun_out/r6v_pair_test.log 2>&1 || { tail -30 gpurun_out/r6v_pair_test.log; exit 1; }
 tail -1 gpurun_out/r6v_pair_test.log
-B="--no-stage --no-ring --secondary-wid 0 --steps 100 --no-cpu-baseline --no-overlap"
+B="--full --no-stage --no-ring --secondary-wid 0 --steps 100 --no-cpu-baseline --no-overlap"
 for rep in 1 2; do
   for p in 0 1; do
     timeout -k 10 300 python bench.py $B --pipeline $p > gpurun_out/r6v_b_p$p$rep.json 2>gpurun_out/r6v_b.err || { tail -5 gpurun_out/r6v_b.err; exit 1; }

@@ -96,6 +96,52 @@ int mvs_score_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* 
  * d_rec 16-B aligned; mvs_pack_accepted reads it with d_count = NULL. */
 int mvs_score_device_rec(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref, int wid,
                          double min_ncc, double* d_xy, int64_t* d_rec, void* stream);
+/* Plane-warped, per-view reprojected photo-consistency test (no reference
+ * counterpart: photo_consistenecy_test cuts every view's window at the
+ * reference view's pixel, MVS2.py:68, and never uses the patch normal).
+ * Candidate i: centre c[3i..], unit normal nrm[3i..] pointing towards the
+ * cameras (NOT checked or normalised), reference view r = ref[i].
+ * Cameras: rotation = mvs_ctx_rproj's, translation t, fx fy cx cy (no skew),
+ * O_v = -Rp_v^T t_v; integer coordinates are pixel centres; gray = the
+ * context's gray stack.
+ *   1. (x, y) = projection of c into r -> xy (bit-equal to mvs_score's).
+ *   2. The candidate is invalid (count 0, empty mask, avg 0, every ncc nan)
+ *      unless depth in r > 0, x >= 0, y >= 0, the window
+ *      [x0-wid, x0+wid] x [y0-wid, y0+wid] around (x0, y0) = (int(x), int(y))
+ *      lies inside [0, W-1] x [0, H-1], nrm.(O_r - c) > min_cos |O_r - c|,
+ *      and the reference window a is not constant (N sum a^2 - (sum a)^2 > 0,
+ *      N = (2 wid + 1)^2).
+ *   3. Every window pixel q goes to the patch plane: d = Rp_r^T ((q.x-cx_r)/
+ *      fx_r, (q.y-cy_r)/fy_r, 1), X = O_r + d (nrm.(c-O_r)) / (nrm.d).
+ *   4. A view v != r is tested when nrm.(O_v - c) > min_cos |O_v - c|.  It
+ *      fails (ncc nan, bit clear) unless every X has depth > 0 in v, every
+ *      sample position (sx, sy) = projection of X into v has 0 <= sx <= W-1,
+ *      0 <= sy <= H-1, and the warped window b is not constant.
+ *   5. b = bilinear sample in difference form: ix = floor(sx), ax = sx - ix,
+ *      ix1 = min(ix+1, W-1) (same in y); top = g00 + ax (g01 - g00), bot =
+ *      g10 + ax (g11 - g10), b = top + ay (bot - top) -- exact on a constant
+ *      neighbourhood, so a flat warped window has D_b = 0 and fails.
+ *   6. ncc = (N sum ab - sum a sum b) / sqrt(D_a D_b) * N/(N-1) (ctNcc's
+ *      scaling, MVS2.py:39-43); the view passes when ncc > min_ncc.
+ * Positions, samples and sums are binary64; results are deterministic.
+ * Outputs as mvs_score: xy (n*2), mask (n*words), count, avg = mean ncc of
+ * the passing views; ncc[i*V + v] (binary64; nan for r, culled and failed
+ * views).  avg and ncc may be NULL.  wid in 1..5, min_cos in [0, 1).
+ * n = 0 returns MVS_OK, launches nothing and touches no context state;
+ * MVS_E_ARG (message in mvs_last_error) for wid or min_cos out of range, a
+ * NULL required pointer, n < 0 and (host call) a ref outside 0..V-1.
+ * The call uses none of the scorers' scratch or counter sets (one kernel,
+ * k_score_warp, reading the scene only): it may be interleaved freely with
+ * every other call.  Host pointers; synchronous. */
+int mvs_score_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                     int wid, double min_ncc, double min_cos, double* xy, uint64_t* mask,
+                     int32_t* count, double* avg, double* ncc);
+/* Same on device pointers, stream-ordered (NULL = the context's stream); a
+ * ref outside 0..V-1 makes its candidate invalid with xy = nan. */
+int mvs_score_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm,
+                            const int32_t* d_ref, int wid, double min_ncc, double min_cos,
+                            double* d_xy, uint64_t* d_mask, int32_t* d_count, double* d_avg,
+                            double* d_ncc, void* stream);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

@@ -110,6 +110,12 @@ def photo_consistency_batch(ctx, centroids, ref_views, MIN_NCC=0.7, wid=5):
     return ctx.score(centroids, ref_views, MIN_NCC, wid)
 
 
+def photo_consistency_warped(ctx, centroids, normals, ref_views, MIN_NCC=0.7, wid=5, min_cos=0.0):
+    """Batched plane-warped photo test (no reference counterpart; see
+    MvsContext.score_warped): (xy, mask, count, avg) per candidate."""
+    return ctx.score_warped(centroids, normals, ref_views, MIN_NCC, wid, min_cos)
+
+
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):
     """MVS2.py:176-295 on the GPU.  Returns None like the reference; the run's
     counters are left in MVS2.last_stats.

@@ -37,6 +37,10 @@ SIGNATURES = [
                                         ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     ("mvs_score_device_rec", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_double,
                                             _vp, _vp, _vp]),
+    ("mvs_score_warped", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_double, _dp, _u64p, _i32p, _dp, _dp]),
+    ("mvs_score_warped_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
+                                               ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -364,6 +368,59 @@ class MvsContext:
         rc = load().mvs_score_device_rec(self._h, n, c.data_ptr(), ref.data_ptr(), int(wid), float(min_ncc),
                                          xy.data_ptr(), rec.data_ptr(), stream if stream is not None else None)
         check(rc, self._h, "mvs_score_device_rec")
+
+    def score_warped(self, c, nrm, ref, min_ncc=0.7, wid=5, min_cos=0.0, want_ncc=False):
+        """Plane-warped, per-view reprojected photo test (mvs_score_warped) on
+        host arrays: the reference window of patch (c, nrm) in view ref is
+        carried through the patch plane into every other view whose camera the
+        normal faces (cosine > min_cos), sampled bilinearly and compared with
+        ctNcc's scaling.  nrm: unit normals pointing towards the cameras (not
+        checked).  Call it where the patch normal is known and the views differ
+        enough that windows at one pixel no longer show the same surface;
+        `score` is the reference's test.
+
+        Returns xy (n,2), mask (n,words) uint64, count (n,), avg (n,) and, with
+        want_ncc, ncc (n,V) float64 (nan for ref, culled and failed views)."""
+        c = _c(c, np.float64).reshape(-1, 3)
+        nrm = _c(nrm, np.float64).reshape(-1, 3)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        if len(c) != n or len(nrm) != n:
+            raise RuntimeError("c, nrm and ref lengths differ")
+        xy = np.empty((n, 2))
+        mask = np.empty((n, self.words), np.uint64)
+        count = np.empty(n, np.int32)
+        avg = np.empty(n)
+        ncc = np.empty((n, self.V)) if want_ncc else None
+        rc = load().mvs_score_warped(self._h, n, _p(c, _dp), _p(nrm, _dp), _p(ref, _i32p), int(wid),
+                                     float(min_ncc), float(min_cos), _p(xy, _dp), _p(mask, _u64p),
+                                     _p(count, _i32p), _p(avg, _dp), _p(ncc, _dp) if want_ncc else None)
+        check(rc, self._h, "mvs_score_warped")
+        return (xy, mask, count, avg, ncc) if want_ncc else (xy, mask, count, avg)
+
+    def score_warped_device(self, c, nrm, ref, xy, mask, count, avg=None, ncc=None, min_ncc=0.7, wid=5,
+                            min_cos=0.0, stream=None):
+        """score_warped on torch device tensors (contiguous: c, nrm float64
+        (n,3), ref int32 (n,), xy float64 (n,2), mask int64 (n,words), count
+        int32 (n,), avg float64 (n,) or None, ncc float64 (n,V) or None);
+        stream-ordered (stream = a hipStream_t handle, None = the context's)."""
+        n = int(ref.numel())
+        want = [("c", c, 8, (n, 3)), ("nrm", nrm, 8, (n, 3)), ("ref", ref, 4, (n,)), ("xy", xy, 8, (n, 2)),
+                ("mask", mask, 8, (n, self.words)), ("count", count, 4, (n,))]
+        if avg is not None:
+            want.append(("avg", avg, 8, (n,)))
+        if ncc is not None:
+            want.append(("ncc", ncc, 8, (n, self.V)))
+        for name, x, size, shape in want:
+            # the kernel indexes rows at a fixed pitch
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"score_warped_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_score_warped_device(self._h, n, c.data_ptr(), nrm.data_ptr(), ref.data_ptr(), int(wid),
+                                            float(min_ncc), float(min_cos), xy.data_ptr(), mask.data_ptr(),
+                                            count.data_ptr(), avg.data_ptr() if avg is not None else None,
+                                            ncc.data_ptr() if ncc is not None else None,
+                                            stream if stream is not None else None)
+        check(rc, self._h, "mvs_score_warped_device")
 
     def pack_accepted(self, offset, count, mask, vlb, out, stream=None, c=None):
         """mvs_pack_accepted: the accepted candidates (count >= vlb) of a scored

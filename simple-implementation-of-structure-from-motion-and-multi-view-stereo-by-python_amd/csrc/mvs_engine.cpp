@@ -306,6 +306,11 @@ struct mvs_ctx {
     DevBuf<double> s_c, s_xy, s_avg;
     DevBuf<int32_t> s_ref, s_count;
     DevBuf<uint64_t> s_mask;
+    // mvs_score_warped's host-pointer buffers: [c, nrm], [xy, avg], ref, mask,
+    // count, ncc (its own: the call shares nothing with the scorers above)
+    DevBuf<double> w_in, w_out, w_ncc;
+    DevBuf<int32_t> w_ref, w_count;
+    DevBuf<uint64_t> w_mask;
     // tiled scorer scratch
     DevBuf<int32_t> t_tiles, t_cand;
     // mvs_pack_accepted: the pack's row counter and chunk ticket (k_acc_pack
@@ -1600,6 +1605,83 @@ int mvs_score(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, int 
         HIPCHK(hipMemcpyAsync(mask, ctx->s_mask.p, n * words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(count, ctx->s_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(avg, ctx->s_avg.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// argument checks shared by the two entry points of the plane-warped test
+static int warp_check(mvs_ctx* ctx, int64_t n, bool ptrs_ok, int wid, double min_cos) {
+    if (n < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_score_warped: n < 0"});
+    if (n > ((int64_t)1 << 31)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_score_warped: n above 2^31"});
+    if (wid < 1 || wid > MVS_MAX_WID) return set_err(ctx, Fail{MVS_E_ARG, "mvs_score_warped: wid must be in 1..5"});
+    if (!(min_cos >= 0.0 && min_cos < 1.0))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_score_warped: min_cos must be in [0, 1)"});
+    if (n > 0 && !ptrs_ok) return set_err(ctx, Fail{MVS_E_ARG, "mvs_score_warped: null pointer (only avg and ncc may be NULL)"});
+    return 0;
+}
+
+static void warp_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                        int wid, double min_ncc, double min_cos, double* d_xy, uint64_t* d_mask, int32_t* d_count,
+                        double* d_avg, double* d_ncc, hipStream_t s) {
+    WarpArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.min_ncc = min_ncc;
+    a.min_cos = min_cos;
+    a.xy = d_xy;
+    a.mask = d_mask;
+    a.count = d_count;
+    a.avg = d_avg;
+    a.ncc = d_ncc;
+    if (mvs_launch_score_warp(&ctx->sc, &a, wid, s) != 0) throw Fail{MVS_E_HIP, "score_warp launch failed"};
+}
+
+int mvs_score_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                            int wid, double min_ncc, double min_cos, double* d_xy, uint64_t* d_mask,
+                            int32_t* d_count, double* d_avg, double* d_ncc, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = warp_check(ctx, n, d_c && d_nrm && d_ref && d_xy && d_mask && d_count, wid, min_cos)) return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        warp_launch(ctx, n, d_c, d_nrm, d_ref, wid, min_ncc, min_cos, d_xy, d_mask, d_count, d_avg, d_ncc, s);
+        return 0;
+    });
+}
+
+int mvs_score_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref, int wid,
+                     double min_ncc, double min_cos, double* xy, uint64_t* mask, int32_t* count, double* avg,
+                     double* ncc) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = warp_check(ctx, n, c && nrm && ref && xy && mask && count, wid, min_cos)) return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        for (int64_t i = 0; i < n; ++i)
+            if (ref[i] < 0 || ref[i] >= ctx->V) throw Fail{MVS_E_ARG, "mvs_score_warped: ref view out of range"};
+        hipStream_t s = ctx->stream;
+        const int words = ctx->words();
+        const int V = ctx->V;
+        // buffers of this call alone (none of the scorers' scratch)
+        ctx->w_in.ensure(n * 6); ctx->w_ref.ensure(n); ctx->w_out.ensure(n * 3);
+        ctx->w_mask.ensure(n * words); ctx->w_count.ensure(n);
+        if (ncc) ctx->w_ncc.ensure(n * V);
+        double* d_c = ctx->w_in.p;
+        double* d_nrm = ctx->w_in.p + n * 3;
+        double* d_xy = ctx->w_out.p;
+        double* d_avg = ctx->w_out.p + n * 2;
+        HIPCHK(hipMemcpyAsync(d_c, c, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_nrm, nrm, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->w_ref.p, ref, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        warp_launch(ctx, n, d_c, d_nrm, ctx->w_ref.p, wid, min_ncc, min_cos, d_xy, ctx->w_mask.p, ctx->w_count.p,
+                    avg ? d_avg : nullptr, ncc ? ctx->w_ncc.p : nullptr, s);
+        HIPCHK(hipMemcpyAsync(xy, d_xy, n * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(mask, ctx->w_mask.p, n * words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(count, ctx->w_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (avg) HIPCHK(hipMemcpyAsync(avg, d_avg, n * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (ncc) HIPCHK(hipMemcpyAsync(ncc, ctx->w_ncc.p, n * V * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     });

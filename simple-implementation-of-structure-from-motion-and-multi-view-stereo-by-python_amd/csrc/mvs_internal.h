@@ -58,6 +58,21 @@ struct ScoreArgs {
     int rec;              // 1: records [mask words, avg bits] of words + 1 int64 each
 };
 
+// Inputs/outputs of one batch of the plane-warped photo test (k_score_warp,
+// mvs_warp.hip; device pointers).
+struct WarpArgs {
+    int64_t n;
+    const double* c;      // n*3 patch centres
+    const double* nrm;    // n*3 unit normals (towards the cameras; not checked)
+    const int32_t* ref;   // n
+    double min_ncc, min_cos;
+    double* xy;           // n*2 (projection into ref view, as ScoreArgs.xy)
+    uint64_t* mask;       // n*words
+    int32_t* count;       // n
+    double* avg;          // n (may be null)
+    double* ncc;          // n*V (may be null): nan for ref, culled and failed views
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -212,6 +227,9 @@ int mvs_launch_build_scene(const SceneDev* sc, const uint8_t* d_rgb, uint8_t* d_
 // on s immediately before and after the kernel
 int mvs_launch_score(const SceneDev* sc, const ScoreArgs* a, int wid, hipStream_t s,
                      hipEvent_t ev0, hipEvent_t ev1);
+// plane-warped photo test (k_score_warp, mvs_warp.hip): one wave per
+// candidate, no scratch; wid in 1..5
+int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStream_t s);
 // tiled scorer: k_bin (tile buckets, then the work items), k_score_mma or k_score_mma_v
 // (timed by ev0/ev1), k_score_fix
 int mvs_launch_score_tiled(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, int wid,

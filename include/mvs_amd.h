@@ -223,6 +223,14 @@ int mvs_stream_retiring(mvs_ctx* ctx, void* stream);
  * batches.  Diagnostic (bench.py reports the guard-band rate per sweep). */
 int mvs_scorer_stats(mvs_ctx* ctx, int64_t* out);
 
+/* Tiled batches since the context was created whose candidates were binned
+ * into workgroup-private sorted runs (no global atomics) rather than into the
+ * atomic tile buckets: dense batches of the tables scorer (V <= 64) of at most
+ * 256 binning workgroups (2^20 candidates).  Environment, read when the context
+ * is created: MVS_BIN=atomic keeps the atomic buckets everywhere;
+ * MVS_BIN_RUNS_MAX=<k> lowers the workgroup limit. */
+int64_t mvs_bin_runs_batches(mvs_ctx* ctx);
+
 /* ctNcc (MVS2.py:39-43) on n explicit window pairs of npx (<= 128) uint8
  * pixels each (device pointers).  ncc[i] = closed-form value (numpy-order
  * value if force_exact or within 1e-9 of thr; nan for a constant window);

@@ -49,6 +49,7 @@ SIGNATURES = [
                                            _u64p, _i32p, _dp, _dp, _dp, _u8p, _i64p]),
     ("mvs_exact_hits", ctypes.c_int64, [_vp]),
     ("mvs_scorer_stats", ctypes.c_int, [_vp, _i64p]),
+    ("mvs_bin_runs_batches", ctypes.c_int64, [_vp]),
     ("mvs_stream_retiring", ctypes.c_int, [_vp, _vp]),
     ("mvs_kernel_timing", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mvs_kernel_time", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_double),
@@ -294,6 +295,12 @@ class MvsContext:
         out = np.zeros(3, np.int64)
         check(load().mvs_scorer_stats(self._h, _p(out, _i64p)), self._h, "mvs_scorer_stats")
         return {"direct": int(out[0]), "overflow": int(out[1]), "batches": int(out[2])}
+
+    def bin_runs_batches(self):
+        """Tiled batches since the context was created that were binned into
+        workgroup-private sorted runs (mvs_bin_runs_batches); the others used
+        the atomic tile buckets."""
+        return int(load().mvs_bin_runs_batches(self._h))
 
     def rebuild(self, stream=None):
         """Rebuild the device gray stack / view-major copy from the resident

@@ -317,6 +317,12 @@ struct mvs_ctx {
     // leaves both zero)
     DevBuf<unsigned long long> p_ctl;
     DevBuf<int4> t_items;
+    // the runs path's scratch (mvs_internal.h) and the most binning
+    // workgroups it is taken for (env MVS_BIN=atomic: 0; MVS_BIN_RUNS_MAX)
+    DevBuf<int2> t_runs;
+    DevBuf<uint16_t> t_offs;
+    int runs_max = kRunsLimit;
+    int64_t runs_batches = 0;   // tiled batches binned into runs (mvs_bin_runs_batches)
     // SfM front-end scratch (Harris maps, descriptors, match rows)
     DevBuf<float> f_resp, f_dil;
     DevBuf<uint32_t> f_key, f_desc;
@@ -547,6 +553,10 @@ void score_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_r
     // >= 2048 candidates; the direct k_score for small batches
     const bool grouped = ctx->V > MVS_GROUP_VIEWS;
     const bool tiled = ctx->kernel_mode == 2 || (ctx->kernel_mode == 0 && n >= 2048);
+    // an empty batch launches nothing: the counter sets and their parity stay
+    // as they are (the launcher returns before k_bin, which would have zeroed
+    // the other set)
+    if (tiled && n == 0) return;
     if (tiled) {
         TiledArgs t{};
         t.tw = MVS_TILE_W;
@@ -593,12 +603,23 @@ void score_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_r
         t.zero_first = ctx->tiles_clean_ntiles != ntiles ? 1 : 0;
         t.grid = ctx->scorer_wgs;
         t.stats = ctx->d_stats.p;
+        // the runs path's buffers, where the batch is small enough for it (the
+        // launcher decides; every element read is written by k_bin)
+        const int64_t nbin = (n + MVS_BIN_CHUNK - 1) / MVS_BIN_CHUNK;
+        t.runs_max = std::min(ctx->runs_max, kRunsLimit);
+        if (nbin <= t.runs_max) {
+            ctx->t_runs.ensure((size_t)nbin * MVS_BIN_CHUNK);
+            ctx->t_offs.ensure((size_t)nbin * (ntiles + 1));
+            t.runs = ctx->t_runs.p;
+            t.offs = ctx->t_offs.p;
+        }
         ctx->tiles_clean_ntiles = -1;            // dirty until the sequence is queued
         hipEvent_t e0, e1;
         ctx->next_events(&e0, &e1);
         ctx->scratch_acquire(s);
         const bool tab = ctx->ensure_moments(wid, s);
         const MomentsDev mt = ctx->moments(wid);
+        if (mvs_tiled_uses_runs(&ctx->sc, &a, &t, tab ? &mt : nullptr)) ++ctx->runs_batches;
         const int rc = mvs_launch_score_tiled(&ctx->sc, &a, &t, wid, tab ? &mt : nullptr, s, e0, e1);
         if (rc != 0) throw Fail{rc == -3 ? MVS_E_UNSUPPORTED : MVS_E_HIP, "tiled score launch failed"};
         ctx->scratch_release(s);
@@ -1431,6 +1452,12 @@ int mvs_ctx_create(int device, int V, int H, int W, const uint8_t* rgb, const do
         }
         if (const char* sw = std::getenv("MVS_SCORER_WGS")) ctx->scorer_wgs = std::max(0, std::atoi(sw));
         if (const char* tl = std::getenv("MVS_TAB_LIMIT")) ctx->tab_limit = std::max<int64_t>(1, std::atoll(tl));
+        // the binning path: MVS_BIN=atomic keeps the atomic tile buckets
+        // everywhere; MVS_BIN_RUNS_MAX: the most runs (binning workgroups)
+        // the runs path is taken for
+        if (const char* rm = std::getenv("MVS_BIN_RUNS_MAX")) ctx->runs_max = std::min(std::max(0, std::atoi(rm)), kRunsLimit);
+        if (const char* bm = std::getenv("MVS_BIN"))
+            if (!std::strcmp(bm, "atomic")) ctx->runs_max = 0;
         return 0;
     });
     if (rc != 0) {
@@ -1718,6 +1745,8 @@ int mvs_scorer_stats(mvs_ctx* ctx, int64_t* out) {
         return 0;
     });
 }
+
+int64_t mvs_bin_runs_batches(mvs_ctx* ctx) { return ctx ? ctx->runs_batches : 0; }
 
 int mvs_ncc_windows(int64_t n, int npx, const uint8_t* d_a, const uint8_t* d_b, double thr,
                     int force_exact, double* d_ncc, uint8_t* d_pass, void* stream) {

@@ -90,6 +90,20 @@ struct WarpArgs {
 //   scores by the direct path -- bucket overflow (k_bin) and candidates with
 //   a view decision inside the guard band (the tiled scorers, numpy-order
 //   ctNcc there)
+// The runs path (k_score_tab on a dense batch of at most runs_max binning
+// workgroups whose tile counters fit k_bin's LDS; MVS_BIN=atomic turns it
+// off) uses neither tile_count nor sorted: binning workgroup b ranks its
+// candidates privately and writes
+//   runs[b * MVS_BIN_CHUNK + r] = {id, pk}: its binned candidates sorted by
+//   tile (r < offs[b][ntiles] <= MVS_BIN_CHUNK), no global atomic;
+//   offs[b * (ntiles + 1) + k] (uint16): the first entry of tile k in run b;
+//   offs[b][ntiles] the run's total.
+// k_score_tab's work items are then the tiles themselves; the workgroup that
+// takes tile k gathers its list from the nbin runs (rank = entries of the
+// runs before b, then the position inside run b), pushes ranks >= cap to
+// fix_list and scores a tile of more than chunk entries in further rounds.
+// The control block (heads, fix_count, n_items) is used as on the atomic path,
+// and k_bin zeroes the other counter set on both paths.
 #ifndef MVS_TC_STRIDE
 #define MVS_TC_STRIDE 1
 #endif
@@ -141,7 +155,16 @@ struct TiledArgs {
     // finishing workgroup; mvs_scorer_stats): [0] candidates on the direct
     // path's list, [1] of them bucket overflow (k_bin), [2] batches
     unsigned long long* stats;
+    // the runs path (see above): runs[nbin * MVS_BIN_CHUNK], offs[nbin *
+    // (ntiles + 1)]; runs_max: the most binning workgroups it is taken for (0:
+    // never; at most kRunsLimit).  use_runs and nbin are set by the launcher
+    int2* runs;
+    uint16_t* offs;
+    int runs_max;
+    int use_runs;
+    int nbin;
 };
+constexpr int kRunsLimit = 256;   // one run per gathering lane of k_score_tab's first four waves
 // candidates per binning workgroup (k_bin): 1024 threads x MVS_BIN_PER
 #ifndef MVS_BIN_PER
 #define MVS_BIN_PER 4
@@ -234,6 +257,10 @@ int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStr
 // (timed by ev0/ev1), k_score_fix
 int mvs_launch_score_tiled(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, int wid,
                            const MomentsDev* mt, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+// 1 if mvs_launch_score_tiled takes the runs path for this batch (k_score_tab,
+// a dense batch, ntiles within k_bin's LDS, at most t->runs_max binning
+// workgroups, both buffers given), else 0: the atomic tile buckets
+int mvs_tiled_uses_runs(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, const MomentsDev* mt);
 // the window-moment tables of one wid (mvs_score_tab.hip)
 int mvs_launch_moments(const SceneDev* sc, const MomentsDev* mt, hipStream_t s);
 // k_score_tab (V <= 64, the moments from the tables); k_bin has run

@@ -453,7 +453,11 @@ __global__ __launch_bounds__(kScanThreads) void k_item_scan(const TiledArgs t) {
     if (threadIdx.x < kItemSegs) t.n_items[32 * threadIdx.x] = threadIdx.x == 0 ? s_w[kScanThreads / 64] : 0;
 }
 
-template <bool LDSHIST>
+// RUNS (with LDSHIST): the runs path (mvs_internal.h) -- the workgroup's
+// candidates sorted by tile into its own run, from an exclusive scan of its LDS
+// histogram; no global atomic, no tile_count, no implicit-item appends, no
+// fix_list entries (k_score_tab's gather pushes the ranks past cap)
+template <bool LDSHIST, bool RUNS = false>
 __global__ __launch_bounds__(kBinBlock) void k_bin(const SceneDev sc, const ScoreArgs a,
                                                    const TiledArgs t, int wid, const MomentsDev mt) {
     extern __shared__ int32_t hist[];      // [ntiles] local counts, then global bases
@@ -571,6 +575,54 @@ __global__ __launch_bounds__(kBinBlock) void k_bin(const SceneDev sc, const Scor
         }
     }
     STAMP(t1);
+    if constexpr (RUNS) {
+        static_assert(LDSHIST, "the runs come from the LDS histogram");
+        // exclusive scan of hist[0, ntiles): a thread sums its contiguous
+        // tiles, wave scans, one cross-wave step
+        __shared__ int s_w[kBinBlock / 64];
+        __syncthreads();
+        const int per = (t.ntiles + kBinBlock - 1) / kBinBlock;
+        const int k0 = min((int)threadIdx.x * per, t.ntiles), k1 = min(k0 + per, t.ntiles);
+        int mine = 0;
+        for (int k = k0; k < k1; ++k) mine += hist[k];
+        int incl = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int o = __shfl_up(incl, d, 64);
+            if ((threadIdx.x & 63) >= d) incl += o;
+        }
+        if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = incl;
+        __syncthreads();
+        int run = incl - mine, total = 0;
+#pragma unroll
+        for (int w = 0; w < kBinBlock / 64; ++w) {
+            const int c = s_w[w];
+            if (w < (int)(threadIdx.x >> 6)) run += c;
+            total += c;
+        }
+        for (int k = k0; k < k1; ++k) {
+            const int c = hist[k];
+            hist[k] = run;   // start[tile]
+            run += c;
+        }
+        __syncthreads();
+        STAMP(t2);
+        uint16_t* orow = t.offs + (int64_t)blockIdx.x * (t.ntiles + 1);
+        for (int k = threadIdx.x; k <= t.ntiles; k += kBinBlock) orow[k] = (uint16_t)(k < t.ntiles ? hist[k] : total);
+        int2* myrun = t.runs + (int64_t)blockIdx.x * MVS_BIN_CHUNK;
+#pragma unroll
+        for (int k = 0; k < kBinPer; ++k) {
+            const int64_t i = base + (int64_t)k * kBinBlock + threadIdx.x;
+            if (tl[k] < 0) continue;
+            myrun[hist[tl[k]] + lr[k]] = make_int2((int32_t)i, pk[k]);
+        }
+        STAMP(t3);
+        STAMP_ADD_ROW(2048 + blockIdx.x, 0, 1);
+        STAMP_ADD_ROW(2048 + blockIdx.x, 1, t1 - t0);
+        STAMP_ADD_ROW(2048 + blockIdx.x, 2, t2 - t1);
+        STAMP_ADD_ROW(2048 + blockIdx.x, 3, t3 - t2);
+        return;
+    }
     if (LDSHIST) {
         // the workgroup's base in every tile it touched: every thread's
         // returning atomics in flight together (ntiles <= 16 x 1024)
@@ -2512,10 +2564,17 @@ int launch_score_tiled_w(const SceneDev* sc, const ScoreArgs* a, const TiledArgs
     // tiles themselves as its items, in tile order, and needs no k_item_scan
     TiledArgs tv = *t;
     tv.implicit = (!grouped && mt && a->n >= (int64_t)kImplicitMean * t->ntiles) ? 1 : 0;
+    // the runs path: k_score_tab on a dense batch of few enough binning
+    // workgroups (one run per gathering lane); everything else keeps the
+    // atomic tile buckets
+    tv.nbin = nbin;
+    tv.use_runs = mvs_tiled_uses_runs(sc, a, t, mt);
     // with the scene's moment tables k_bin also settles the candidates whose
     // reference window is constant (they pass no view) without binning them
     const MomentsDev mflat = mt ? *mt : MomentsDev{};
-    if (t->ntiles <= kBinLdsTiles)
+    if (tv.use_runs)
+        hipLaunchKernelGGL((k_bin<true, true>), dim3(nbin), dim3(kBinBlock), (size_t)t->ntiles * 4, s, *sc, *a, tv, WID, mflat);
+    else if (t->ntiles <= kBinLdsTiles)
         hipLaunchKernelGGL(k_bin<true>, dim3(nbin), dim3(kBinBlock), (size_t)t->ntiles * 4, s, *sc, *a, tv, WID, mflat);
     else
         hipLaunchKernelGGL(k_bin<false>, dim3(nbin), dim3(kBinBlock), 0, s, *sc, *a, tv, WID, mflat);
@@ -2574,6 +2633,13 @@ extern "C" int mvs_read_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : -1;
 }
 #endif
+
+extern "C" int mvs_tiled_uses_runs(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, const MomentsDev* mt) {
+    const int64_t nbin = (a->n + MVS_BIN_CHUNK - 1) / MVS_BIN_CHUNK;
+    const bool dense = sc->V <= kGroupViews && mt && a->n >= (int64_t)kImplicitMean * t->ntiles;
+    const bool fits = t->ntiles <= kBinLdsTiles && nbin <= std::min(t->runs_max, kRunsLimit);
+    return dense && a->n > 0 && fits && t->runs && t->offs ? 1 : 0;
+}
 
 extern "C" int mvs_launch_build_scene(const SceneDev* sc, const uint8_t* d_rgb, uint8_t* d_stack,
                                       uint8_t* d_gv_base, hipStream_t s) {

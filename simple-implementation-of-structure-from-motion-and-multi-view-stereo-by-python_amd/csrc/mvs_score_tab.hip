@@ -159,7 +159,9 @@ __global__ __launch_bounds__(256) void k_moments(const SceneDev sc, const Moment
 //   1. the item's window region of every view (signed bytes, [view][ROWS][32],
 //      one pad row per view) and its candidate list are in LDS (LDS-DMA,
 //      double-buffered where LDS allows: item k+1's lands while item k is
-//      scored; a barrier per item);
+//      scored; a barrier per item); RUNS: only the region is DMA'd, the list
+//      is gathered from k_bin's workgroup-private runs (g_issue, g_scan,
+//      g_write below) between the units of the round before;
 //   2. wave w takes the item's M-blocks [w nblk / 8, (w+1) nblk / 8) and sorts
 //      its own candidates by row pair (ballots, in its own part of the list:
 //      no workgroup barrier), so that a unit's windows span few K-steps;
@@ -195,6 +197,25 @@ __device__ unsigned long long g_stamps_tab[1024 * 16];
 // issue by fewer waves or later, 10 waves, tail-split items, one workgroup
 // per CU, ...) are in DESIGN.md 4.1 with their logs under profiles/r05/; the
 // code of each is in the git history (round 5), not in this file.
+DEV int wave_sum(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// inclusive scan of x over the wave's 64 lanes (all active) by DPP adds: row
+// shifts by 1, 2, 4, 8, then lane 15 of rows 0 and 2 into rows 1 and 3 and
+// lane 31 into rows 2 and 3 -- no LDS round trips (a shuffle takes one each)
+DEV int wave_scan_add(int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, false);   // row_shr:1
+    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, false);   // row_shr:2
+    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, false);   // row_shr:4
+    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, false);   // row_shr:8
+    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xa, 0xf, false);   // row_bcast:15 to rows 1, 3
+    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xc, 0xf, false);   // row_bcast:31 to rows 2, 3
+    return x;
+}
+
 constexpr int kTabWaves = 8, kTabThreads = 64 * kTabWaves, kTabGrid = 512;
 constexpr int kTabBudget = 80 * 1024 - 512;                 // LDS bytes per workgroup (two per CU)
 constexpr int kTabMinWaves = (2 * kTabWaves + 3) / 4;       // per SIMD
@@ -220,7 +241,7 @@ struct TabGeom {
     static constexpr bool DB = 2 * BUF + FIXED <= kTabBudget;
 };
 
-template <int WID, int NBLK, bool FAST>
+template <int WID, int NBLK, bool FAST, bool RUNS>
 __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const SceneDev sc, const ScoreArgs a, const TiledArgs t,
                                                                const MomentsDev mt, const int4* __restrict__ items,
                                                                const int2* __restrict__ sorted) {
@@ -240,6 +261,7 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
     __shared__ __attribute__((aligned(16))) uint8_t s_cand0[CB], s_cand1[DB ? CB : 16];
     __shared__ __attribute__((aligned(16))) TabInfo s_ti[kTabWaves * 32];
     __shared__ int s_ids[2];
+    __shared__ int s_tot[2];   // runs path: the entries of the tile gathered into each list buffer
     __shared__ double s_recip[65];
 #ifdef MVS_STAMPS
     const unsigned long long t_wg0 = __builtin_amdgcn_s_memrealtime();
@@ -256,11 +278,14 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
     const double kn = (double)NPX / (double)(NPX - 1);
     const float tqf = (float)(a.thr / kn);
     ItemMap im;
-    im.load(t);
+    if constexpr (!RUNS) im.load(t);
     // implicit items: k < ntiles is (tile k, chunk 0), then segment 1's
     // further chunks (k_bin); else k_item_scan's list
-    const bool implicit = t.implicit != 0;
-    const int n_units = implicit ? t.ntiles + t.n_items[32] : im.total();
+    const bool implicit = RUNS || t.implicit != 0;
+    const int n_units = RUNS ? t.ntiles : implicit ? t.ntiles + t.n_items[32] : im.total();
+    // the runs path (mvs_internal.h): the items are the tiles (k_bin appended
+    // none), and a tile's list is gathered from the binning workgroups' runs
+    constexpr bool runs = RUNS;
     int32_t* head = t.head;
     const int16_t* __restrict__ tsb = mt.sb;
     const double* __restrict__ tw = mt.w;
@@ -296,6 +321,121 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
                 __builtin_amdgcn_global_load_lds((const void*)(csrc + 16 * k),
                                                  (void __attribute__((address_space(3)))*)(cbase + (p * kTabThreads + wave * 64) * 16),
                                                  16, 0, 0);
+        }
+    };
+
+    // The runs path's list of (tile, chunk j) into a list buffer: entries
+    // [j chunk, min((j+1) chunk, cap)) of the tile in run order.  Lane l of the
+    // first ceil(nbin / 64) waves owns run b = 64 wave + l: its entries of the
+    // tile are runs[b][offs[b][tile] .. offs[b][tile+1]), their ranks start at
+    // the entries of the runs before b -- the lower waves' counts summed again
+    // by this wave (every gathering wave loads the four count columns: no
+    // workgroup barrier), then a wave scan.  Three steps, so that a round can
+    // put work between them (each waits for the loads of the one before):
+    // g_issue (the count loads), g_scan (ranks, the tile's total to s_tot --
+    // the round's barrier publishes it --, with chunk 0 the ranks past cap to
+    // the direct path's list, as k_bin's bucket overflow on the atomic path;
+    // the first entries' loads), g_write (the entries into the list).
+    // 32-bit element indices from the uniform bases (nbin (ntiles + 1) and
+    // nbin MVS_BIN_CHUNK are below 2^31): one address register per load
+    // DEFER: the three steps spread over the round (below); with four view
+    // blocks the two-buffer configurations have no registers to hold the
+    // entries across a unit, so their steps run back to back
+    constexpr bool DEFER = DB && NBLK < 4;
+    constexpr int GUP = 3;   // entry loads in flight per lane (1.3 entries per run and tile at the headline shape)
+    // one register set for both waits: after g_issue r[jj] = offs[b][tile] |
+    // offs[b][tile + 1] << 16 of run b = 64 jj + lane; after g_scan r[2u],
+    // r[2u + 1] = entry u, r[2 GUP] = entries to copy << 16 | the first one's
+    // list slot, r[2 GUP + 1] = the first one's element of runs
+    struct Gath {
+        uint32_t r[2 * GUP + 2];
+    };
+    static_assert(kRunsLimit / 64 <= 2 * GUP + 2, "the count columns fit the register set");
+    const int g_waves = (t.nbin + 63) >> 6;
+    auto g_issue = [&](int tile, Gath& g) {
+        if (wave >= g_waves) return;
+        const uint16_t* __restrict__ offs = t.offs;
+        const int ol = opaque(lane);
+        // the two neighbouring 16-bit offsets by one 4-byte load (2-byte
+        // aligned); columns above this wave's own are not needed
+#pragma unroll
+        for (int jj = 0; jj < kRunsLimit / 64; ++jj) {
+            g.r[jj] = 0u;
+            if (jj <= wave) {
+                const int k = min(64 * jj + ol, t.nbin - 1) * (t.ntiles + 1) + tile;
+                __builtin_memcpy(&g.r[jj], offs + k, 4);
+            }
+        }
+    };
+    auto g_scan = [&](int tile, int j, Gath& g, auto bufc) {
+        constexpr int buf = decltype(bufc)::value;
+        if (wave >= g_waves) return;
+        const int2* __restrict__ rsrc = t.runs;
+        const int ol = opaque(lane);
+        // this lane's entries in the lower waves' columns, summed over the
+        // wave once; its own column scanned
+        int low = 0, cnt = 0, o0 = 0;
+#pragma unroll
+        for (int jj = 0; jj < kRunsLimit / 64; ++jj) {
+            const int a0 = (int)(g.r[jj] & 0xffffu), a1 = (int)(g.r[jj] >> 16);
+            const int c = 64 * jj + ol < t.nbin ? a1 - a0 : 0;
+            if (jj < wave) low += c;
+            if (jj == wave) { cnt = c; o0 = a0; }
+        }
+        const int pre = __builtin_amdgcn_readlane(wave_scan_add(low), 63);
+        const int incl = wave_scan_add(cnt);
+        const int rank0 = pre + incl - cnt;   // the tile rank of this run's first entry
+        if (wave == g_waves - 1 && ol == 63) s_tot[buf] = pre + incl;
+        const int lo = j * t.chunk, hi = min(lo + t.chunk, t.cap);
+        const int e0 = max(lo - rank0, 0), e1 = min(cnt, hi - rank0);
+        const int sb = (64 * wave + ol) * MVS_BIN_CHUNK + o0;   // the run's first entry of the tile
+        const int n = max(e1 - e0, 0);
+        g.r[2 * GUP] = (uint32_t)((n << 16) | (n ? rank0 - lo + e0 : 0));
+        g.r[2 * GUP + 1] = (uint32_t)(sb + e0);
+        if (n) {
+#pragma unroll
+            for (int u = 0; u < GUP; ++u) {
+                const int2 v = rsrc[sb + e0 + min(u, n - 1)];
+                g.r[2 * u] = (uint32_t)v.x;
+                g.r[2 * u + 1] = (uint32_t)v.y;
+            }
+        }
+        if (j == 0) {
+            // ranks past cap: each such run's tail copied by the whole wave
+            const int f0 = max(t.cap - rank0, 0);
+            const int ov = max(cnt - f0, 0);
+            uint64_t om = __ballot(ov > 0);
+            if (om) {
+                int slot = 0;
+                if (ov > 0) slot = atomicAdd(t.fix_count, ov);
+                if (t.stats) {
+                    const int tot = wave_sum(ov);
+                    if (ol == 0) atomicAdd(&t.stats[1], (unsigned long long)tot);
+                }
+                for (; om; om &= om - 1) {
+                    const int l = __builtin_ctzll(om);
+                    const int n_l = __builtin_amdgcn_readlane(ov, l);
+                    const int src_l = __builtin_amdgcn_readlane(sb + f0, l);
+                    const int slot_l = __builtin_amdgcn_readlane(slot, l);
+                    for (int e = ol; e < n_l; e += 64) {
+                        const int2 v = rsrc[src_l + e];
+                        t.fix_list[slot_l + e] = make_int4(v.x, tile, v.y, 0);
+                    }
+                }
+            }
+        }
+    };
+    auto g_write = [&](const Gath& g, auto bufc) {
+        if (wave >= g_waves) return;
+        const int n = (int)(g.r[2 * GUP] >> 16);
+        int2* dst = (int2*)cand_buf(bufc) + (g.r[2 * GUP] & 0xffffu);
+        if (n) {
+#pragma unroll
+            for (int u = 0; u < GUP; ++u)
+                if (u < n) dst[u] = make_int2((int)g.r[2 * u], (int)g.r[2 * u + 1]);
+            const int2* __restrict__ rsrc = t.runs;
+            const int src = (int)g.r[2 * GUP + 1];
+            for (int e = GUP; e < n; ++e) dst[e] = rsrc[src + e];
         }
     };
 
@@ -357,17 +497,24 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
         // list is staged as a whole chunk), so it goes out before the count
         const int2 it = implicit && cur < t.ntiles ? make_int2(cur, 0) : item_v(cur);
         const int tile = __builtin_amdgcn_readfirstlane(it.x), j = __builtin_amdgcn_readfirstlane(it.y);
-        stage(make_int4(tile, tile * t.cap + j * t.chunk, 0, min(t.chunk, t.cap - j * t.chunk)),
+        stage(make_int4(tile, tile * t.cap + j * t.chunk, 0, runs ? 0 : min(t.chunk, t.cap - j * t.chunk)),
               std::integral_constant<int, 0>{});
-        dcur = desc(it, count_v(it.x));
+        if constexpr (runs) {
+            Gath g;
+            g_issue(tile, g);
+            g_scan(tile, 0, g, std::integral_constant<int, 0>{});
+            g_write(g, std::integral_constant<int, 0>{});
+        }
+        dcur = desc(it, runs ? 0 : count_v(it.x));
     }
+    int curj = 0;   // runs path: the chunk of the tile this round scores
     int2 it1 = make_int2(0, 0);
     int pend = nx1;   // thread 0's: the next item, published at round 0's barrier
     __syncthreads();   // everyone has read s_ids before they are rewritten
 
     auto round = [&](auto bufc) -> bool {
         constexpr int buf = decltype(bufc)::value;
-        const int nc = dcur.z;
+        int nc = dcur.z;
         const uint8_t* reg = region_buf(bufc);
         int2* cand = (int2*)cand_buf(bufc);
         const int zoff = RB;   // the zero row, relative to the region buffer
@@ -380,16 +527,41 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
         // item k+1 (claimed last round), its region and list into the other
         // buffer and its count
         nx1 = __builtin_amdgcn_readfirstlane(s_ids[0]);
-        if (nx1 < n_units) {
+        // runs path: this list's count arrived through LDS; a tile with more
+        // entries below cap than one chunk takes further rounds of this
+        // workgroup (the next item waits, nothing is claimed meanwhile)
+        bool more = false;
+        if (runs) {
+            const int below = min(__builtin_amdgcn_readfirstlane(s_tot[buf]), t.cap);
+            nc = max(min(below - curj * t.chunk, t.chunk), 0);
+            more = (curj + 1) * t.chunk < below;
+        }
+        if (more) {
+            it1 = make_int2(dcur.x, curj + 1);
+        } else if (nx1 < n_units) {
             const int2 iv = item_v(nx1);   // implicit: computed; else a load waited for here
             it1 = make_int2(__builtin_amdgcn_readfirstlane(iv.x), __builtin_amdgcn_readfirstlane(iv.y));
         }
         const int j1 = it1.y;
-        const int4 dst1 = make_int4(it1.x, it1.x * t.cap + j1 * t.chunk, 0, min(t.chunk, t.cap - j1 * t.chunk));
+        const int4 dst1 = make_int4(it1.x, it1.x * t.cap + j1 * t.chunk, 0,
+                                    runs ? 0 : min(t.chunk, t.cap - j1 * t.chunk));
+        // runs path: the next list's count loads go out here, its ranks and
+        // entry loads after this wave's first unit, the entries are written
+        // after its last: both waits fall behind a unit's work
+        const bool nextv = nx1 < n_units || more;
+        Gath g;
         if constexpr (DB) {
-            if (nx1 < n_units) stage(dst1, std::integral_constant<int, buf ^ 1>{});
+            if (nextv) {
+                if constexpr (runs) g_issue(it1.x, g);
+                if constexpr (runs && !DEFER) {
+                    g_scan(it1.x, j1, g, std::integral_constant<int, buf ^ 1>{});
+                    g_write(g, std::integral_constant<int, buf ^ 1>{});
+                }
+                stage(dst1, std::integral_constant<int, buf ^ 1>{});
+            }
         }
-        const int c1 = count_v(it1.x);
+        int c1 = 0;
+        if constexpr (!runs) c1 = count_v(it1.x);
         TSTAMP(ts1b);
         TSTAMP_ADD(7, ts1b - ts1);
         const int ty = dcur.x / t.ntx, tx = dcur.x - ty * t.ntx;
@@ -696,20 +868,38 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
             TSTAMP_ADD(4, nh);
             // thread 0 claims item k+2 after wave 0's first unit: less held
             // back when the queue runs dry
-            if (fb == b0 && tid == 0 && nx1 < n_units) pend = claim();
+            if (fb == b0 && tid == 0 && nx1 < n_units && !more) pend = claim();
+            if constexpr (runs && DEFER) {
+                if (fb == b0 && nextv) g_scan(it1.x, j1, g, std::integral_constant<int, buf ^ 1>{});
+            }
         }
-        if (b0 >= b1 && tid == 0 && nx1 < n_units) pend = claim();
+        if (b0 >= b1 && tid == 0 && nx1 < n_units && !more) pend = claim();
+        if constexpr (runs && DEFER) {
+            if (b0 >= b1 && nextv) g_scan(it1.x, j1, g, std::integral_constant<int, buf ^ 1>{});
+            if (nextv) g_write(g, std::integral_constant<int, buf ^ 1>{});
+        }
         TSTAMP(ts3);
         if (wave == 0) TSTAMP_ADD(0, 1);
         TSTAMP_ADD(1, ts1 - ts0);
         TSTAMP_ADD(2, ts2 - ts1);
         TSTAMP_ADD(3, ts3 - ts2);
-        if (nx1 >= n_units) return false;
+        if (nx1 >= n_units && !more) return false;
         if constexpr (!DB) {
             // one buffer: every wave is done with it before the next item lands
             __syncthreads();
+            if constexpr (runs) {
+                Gath g0;
+                g_issue(it1.x, g0);
+                g_scan(it1.x, j1, g0, std::integral_constant<int, 0>{});
+                g_write(g0, std::integral_constant<int, 0>{});
+            }
             stage(dst1, std::integral_constant<int, 0>{});
         }
+        if (more) {
+            ++curj;   // same tile; the claimed item is published again next round
+            return true;
+        }
+        curj = 0;
         cur = nx1;
         dcur = desc(it1, c1);
         return true;
@@ -737,12 +927,18 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
 template <int WID, int NBLK>
 int launch_tab(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, const MomentsDev* mt, hipStream_t s) {
     const dim3 grid(t->grid > 0 ? std::min(t->grid, kTabGrid) : kTabGrid);
-    if (fabs(a->thr) >= 0.01)
-        hipLaunchKernelGGL((k_score_tab<WID, NBLK, true>), grid, dim3(kTabThreads), 0, s, *sc, *a, *t, *mt,
-                           (const int4*)t->items, (const int2*)t->sorted);
-    else
-        hipLaunchKernelGGL((k_score_tab<WID, NBLK, false>), grid, dim3(kTabThreads), 0, s, *sc, *a, *t, *mt,
-                           (const int4*)t->items, (const int2*)t->sorted);
+#define MVS_TAB_LAUNCH(FAST_, RUNS_)                                                                            \
+    hipLaunchKernelGGL((k_score_tab<WID, NBLK, FAST_, RUNS_>), grid, dim3(kTabThreads), 0, s, *sc, *a, *t, *mt, \
+                       (const int4*)t->items, (const int2*)t->sorted)
+    const bool fast = fabs(a->thr) >= 0.01;
+    if (t->use_runs) {
+        if (fast) MVS_TAB_LAUNCH(true, true);
+        else MVS_TAB_LAUNCH(false, true);
+    } else {
+        if (fast) MVS_TAB_LAUNCH(true, false);
+        else MVS_TAB_LAUNCH(false, false);
+    }
+#undef MVS_TAB_LAUNCH
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -142,6 +142,63 @@ int mvs_score_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const do
                             const int32_t* d_ref, int wid, double min_ncc, double min_cos,
                             double* d_xy, uint64_t* d_mask, int32_t* d_count, double* d_avg,
                             double* d_ncc, void* stream);
+/* One level of a fixed-grid depth and normal refinement of patches against
+ * the plane-warped photo test (no reference counterpart: the reference never
+ * refines a patch).  Cameras, gray values, pixel conventions and the bilinear
+ * form are mvs_score_warped's.
+ * Candidate i: centre c[3i..], unit normal nrm[3i..] towards the cameras (NOT
+ * checked or normalised), reference view r = ref[i], a view list
+ * views[i*tv .. i*tv+tv-1] (tv in 1..32, unused slots -1 at the end; |T| = the
+ * number of entries >= 0) and a depth step dstep[i] > 0 in world units.
+ * Scalars: wid in 1..5, min_cos in [0, 1), kd in 0..3, ka in 0..2, astep >= 0
+ * in radians, step_scale > 0, ka astep step_scale <= 1.2.
+ *   1. Window.  (x, y) = mvs_score_warped's projection of c into r, (x0, y0) =
+ *      (int(x), int(y)).  The candidate must pass step 2 of mvs_score_warped
+ *      with c and nrm, |T| >= 1 and dstep > 0.  The window and its values a
+ *      are the same for every hypothesis (c_k below lies on the ray of c, so
+ *      nothing is projected again).
+ *   2. Grid.  u = (c - O_r) / |c - O_r|, c_k = c + (k dstep step_scale) u for
+ *      k = -kd..kd.  m = the index of the smallest |nrm_m| (lowest index on
+ *      ties), e1 = (nrm x axis_m) / |nrm x axis_m|, e2 = nrm x e1,
+ *      n_ij = (nrm + tan(i alpha) e1 + tan(j alpha) e2) / |...| with alpha =
+ *      astep step_scale for i, j = -ka..ka; n_00 = nrm as given.  The 2 ka + 1
+ *      tangents are computed once on the host (libm tan).  Hypothesis
+ *      h = ((k + kd) A + (j + ka)) A + (i + ka), A = 2 ka + 1,
+ *      H = (2 kd + 1) A^2; the centre hypothesis (H - 1) / 2 is the input.
+ *   3. Score.  Hypothesis h is the plane through c_k with normal n_ij; every
+ *      window pixel's ray meets it as in step 3 of mvs_score_warped.  It is
+ *      valid only when n_ij.(O_r - c_k) > min_cos |O_r - c_k| and every list
+ *      view passes the facing test of step 4 with (n_ij, c_k) and gets a
+ *      finite ncc from steps 4-6.  score[h] = (sum of the list's ncc, in list
+ *      order) / |T|, nan when invalid.  There is no min_ncc: the list is the
+ *      caller's choice of views.
+ *   4. Choice.  The centre hypothesis is kept unless another valid one scores
+ *      strictly higher; among the others the highest score wins, ties go to
+ *      the lowest index.  best[i] = the chosen index, score_best[i] = its
+ *      score (the same bits as scores[i*H + best]), c_out / nrm_out = its c_k
+ *      and n_ij -- for the centre the inputs, bit for bit.  With no valid
+ *      hypothesis or an invalid candidate: best = -1, score_best = nan,
+ *      c_out / nrm_out = the inputs bit for bit, every scores entry nan.
+ * scores (n*H) may be NULL.  c_out / nrm_out must not overlap c / nrm.
+ * Binary64 throughout; results are deterministic.  n = 0 returns MVS_OK and
+ * launches nothing.  MVS_E_ARG (message in mvs_last_error) for a scalar out of
+ * range, a NULL required pointer, n < 0 and (host call) a ref outside 0..V-1
+ * or a list entry outside -1..V-1, equal to r, repeated, or following a -1.
+ * The call uses none of the scorers' scratch or counter sets (one kernel,
+ * k_refine_warp, reading the scene only): it may be interleaved freely with
+ * every other call.  Host pointers; synchronous. */
+int mvs_refine_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                      const int32_t* views, int tv, const double* dstep, int wid, double min_cos, int kd,
+                      int ka, double astep, double step_scale, double* c_out, double* nrm_out,
+                      int32_t* best, double* score_best, double* scores);
+/* Same on device pointers, stream-ordered (NULL = the context's stream); a
+ * ref outside 0..V-1 or a list that breaks the rules above makes its
+ * candidate invalid. */
+int mvs_refine_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm,
+                             const int32_t* d_ref, const int32_t* d_views, int tv, const double* d_dstep,
+                             int wid, double min_cos, int kd, int ka, double astep, double step_scale,
+                             double* d_c_out, double* d_nrm_out, int32_t* d_best, double* d_score_best,
+                             double* d_scores, void* stream);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

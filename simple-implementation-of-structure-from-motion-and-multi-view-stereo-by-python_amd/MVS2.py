@@ -116,6 +116,14 @@ def photo_consistency_warped(ctx, centroids, normals, ref_views, MIN_NCC=0.7, wi
     return ctx.score_warped(centroids, normals, ref_views, MIN_NCC, wid, min_cos)
 
 
+def refine_patches_warped(ctx, centroids, normals, ref_views, MIN_NCC=0.7, wid=5, min_cos=0.0, **kw):
+    """Depth and normal refinement of patches against the plane-warped photo
+    test (no reference counterpart; see MvsContext.refine_warped, which takes
+    the remaining keywords): refined centroids, refined normals, the final
+    test's (xy, mask, count, avg) and the info dict."""
+    return ctx.refine_warped(centroids, normals, ref_views, wid=wid, min_ncc=MIN_NCC, min_cos=min_cos, **kw)
+
+
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):
     """MVS2.py:176-295 on the GPU.  Returns None like the reference; the run's
     counters are left in MVS2.last_stats.

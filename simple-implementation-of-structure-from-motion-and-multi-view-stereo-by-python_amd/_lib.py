@@ -6,6 +6,7 @@ reference's main() catches, main.py:43-46).
 """
 import atexit
 import ctypes
+import math
 import os
 import weakref
 
@@ -41,6 +42,12 @@ SIGNATURES = [
                                         ctypes.c_double, _dp, _u64p, _i32p, _dp, _dp]),
     ("mvs_score_warped_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                                ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mvs_refine_warped", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, _i32p, ctypes.c_int, _dp,
+                                         ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_double, ctypes.c_double, _dp, _dp, _i32p, _dp, _dp]),
+    ("mvs_refine_warped_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
+                                                ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -253,6 +260,9 @@ class MvsContext:
         check(rc, None, "mvs_ctx_create")
         self._h = h
         self.device = device
+        self._K = K.reshape(self.V, 3, 3).copy()   # refine_depth_steps
+        self._t = t.copy()
+        self._refine_stream = None   # refine_warped's torch side stream
         self._stages = weakref.WeakSet()
         _LIVE.add(self)
 
@@ -428,6 +438,172 @@ class MvsContext:
                                             ncc.data_ptr() if ncc is not None else None,
                                             stream if stream is not None else None)
         check(rc, self._h, "mvs_score_warped_device")
+
+    @staticmethod
+    def refine_hypotheses(kd, ka):
+        """H = (2 kd + 1)(2 ka + 1)^2, the grid size of one refinement level."""
+        return (2 * int(kd) + 1) * (2 * int(ka) + 1) ** 2
+
+    def refine_warped_level(self, c, nrm, ref, views, dstep, wid=5, min_cos=0.0, kd=2, ka=1,
+                            astep=math.radians(8), step_scale=1.0, want_scores=False):
+        """One level of the fixed-grid depth and normal refinement
+        (mvs_refine_warped) on host arrays: the H = (2 kd + 1)(2 ka + 1)^2
+        plane hypotheses around patch (c, nrm) -- depths k dstep step_scale
+        along the reference ray, normals tilted by tan(i astep step_scale) along
+        two tangents -- are scored by the mean warped ncc over the patch's view
+        list views[i] (int32 (n, tv), -1 padded at the end), and the best is
+        chosen; the input patch is kept unless another scores strictly higher.
+
+        Returns c_out (n,3), nrm_out (n,3), best (n,) int32 (-1: nothing valid),
+        score_best (n,) and, with want_scores, scores (n, H)."""
+        c = _c(c, np.float64).reshape(-1, 3)
+        nrm = _c(nrm, np.float64).reshape(-1, 3)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        views = _c(views, np.int32)
+        if views.ndim != 2 or len(views) != n:
+            raise RuntimeError("views must be (n, tv) int32")
+        tv = views.shape[1]
+        dstep = _c(dstep, np.float64).reshape(-1)
+        if len(c) != n or len(nrm) != n or len(dstep) != n:
+            raise RuntimeError("c, nrm, ref, views and dstep lengths differ")
+        c_out = np.empty((n, 3))
+        nrm_out = np.empty((n, 3))
+        best = np.empty(n, np.int32)
+        score_best = np.empty(n)
+        scores = np.empty((n, self.refine_hypotheses(kd, ka))) if want_scores and 0 <= kd <= 3 and 0 <= ka <= 2 \
+            else None
+        rc = load().mvs_refine_warped(self._h, n, _p(c, _dp), _p(nrm, _dp), _p(ref, _i32p), _p(views, _i32p),
+                                      int(tv), _p(dstep, _dp), int(wid), float(min_cos), int(kd), int(ka),
+                                      float(astep), float(step_scale), _p(c_out, _dp), _p(nrm_out, _dp),
+                                      _p(best, _i32p), _p(score_best, _dp),
+                                      _p(scores, _dp) if scores is not None else None)
+        check(rc, self._h, "mvs_refine_warped")
+        return (c_out, nrm_out, best, score_best, scores) if want_scores else (c_out, nrm_out, best, score_best)
+
+    def refine_warped_level_device(self, c, nrm, ref, views, dstep, c_out, nrm_out, best, score_best, scores=None,
+                                   wid=5, min_cos=0.0, kd=2, ka=1, astep=math.radians(8), step_scale=1.0,
+                                   stream=None):
+        """refine_warped_level on torch device tensors (contiguous: c, nrm,
+        c_out, nrm_out float64 (n,3), ref, best int32 (n,), views int32 (n,tv),
+        dstep, score_best float64 (n,), scores float64 (n,H) or None);
+        stream-ordered (stream = a hipStream_t handle, None = the context's).
+        c_out / nrm_out must be other tensors than c / nrm."""
+        n = int(ref.numel())
+        tv = int(views.shape[1]) if views.dim() == 2 else 0
+        want = [("c", c, 8, (n, 3)), ("nrm", nrm, 8, (n, 3)), ("ref", ref, 4, (n,)), ("views", views, 4, (n, tv)),
+                ("dstep", dstep, 8, (n,)), ("c_out", c_out, 8, (n, 3)), ("nrm_out", nrm_out, 8, (n, 3)),
+                ("best", best, 4, (n,)), ("score_best", score_best, 8, (n,))]
+        if scores is not None:
+            want.append(("scores", scores, 8, (n, self.refine_hypotheses(kd, ka))))
+        for name, x, size, shape in want:
+            # the kernel indexes rows at a fixed pitch
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(
+                    f"refine_warped_level_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_refine_warped_device(self._h, n, c.data_ptr(), nrm.data_ptr(), ref.data_ptr(),
+                                             views.data_ptr(), tv, dstep.data_ptr(), int(wid), float(min_cos),
+                                             int(kd), int(ka), float(astep), float(step_scale), c_out.data_ptr(),
+                                             nrm_out.data_ptr(), best.data_ptr(), score_best.data_ptr(),
+                                             scores.data_ptr() if scores is not None else None,
+                                             stream if stream is not None else None)
+        check(rc, self._h, "mvs_refine_warped_device")
+
+    @staticmethod
+    def refine_view_lists(ncc, min_ncc=0.7, max_views=8):
+        """The view lists refine_warped builds from score_warped's ncc (n, V):
+        per patch the max_views passing views (ncc > min_ncc) with the highest
+        ncc, ties to the lower view index, in ascending view order, padded with
+        -1 -> int32 (n, max_views)."""
+        ncc = np.asarray(ncc, np.float64)
+        n, V = ncc.shape
+        with np.errstate(invalid="ignore"):
+            key = np.where(ncc > min_ncc, ncc, -np.inf)      # nan and failing views last
+        order = np.argsort(-key, axis=1, kind="stable")[:, :max_views]   # stable: ties keep the lower view first
+        keep = np.take_along_axis(key, order, 1) > -np.inf
+        lists = np.where(keep, order, V)                     # V sorts after every view
+        lists.sort(axis=1)
+        lists[lists == V] = -1
+        out = np.full((n, max_views), -1, np.int32)
+        out[:, :lists.shape[1]] = lists
+        return out
+
+    def refine_depth_steps(self, c, ref, depth_px=1.5):
+        """dstep = depth_px * (depth of c in its reference view) / ((fx + fy) / 2):
+        the world size of depth_px pixels at the patch."""
+        c = _c(c, np.float64).reshape(-1, 3)
+        ref = np.asarray(ref).reshape(-1)
+        Rp, t, K = self.rproj(), self._t, self._K
+        depth = Rp[ref, 2, 0] * c[:, 0] + Rp[ref, 2, 1] * c[:, 1] + Rp[ref, 2, 2] * c[:, 2] + t[ref, 2]
+        return depth_px * depth / ((K[ref, 0, 0] + K[ref, 1, 1]) / 2)
+
+    def refine_warped(self, c, nrm, ref, wid=5, min_ncc=0.7, min_cos=0.0, max_views=8, levels=4, kd=2, ka=1,
+                      depth_px=1.5, astep=math.radians(8)):
+        """Coarse-to-fine depth and normal refinement of patches against the
+        plane-warped photo test:
+          1. score_warped with per-view ncc;
+          2. per patch the view list of refine_view_lists (the max_views best
+             passing views);
+          3. dstep = the world size of depth_px pixels at the patch;
+          4. `levels` level calls (refine_warped_level_device) with step_scale
+             = 2^-level, c / nrm ping-ponging between two device buffers, no
+             host synchronisation in between;
+          5. score_warped of the refined patches.
+        A patch with no passing view, or invalid in its reference view, comes
+        back unchanged (best -1 at every level).
+
+        Returns c' (n,3), nrm' (n,3), (xy, mask, count, avg) of the final test
+        and an info dict: views (n, max_views), best (levels, n), score_first
+        (n,) the first level's centre score, score_last (n,) the last level's
+        best score."""
+        import torch
+        c = _c(c, np.float64).reshape(-1, 3)
+        nrm = _c(nrm, np.float64).reshape(-1, 3)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        levels = int(levels)
+        if levels < 1:
+            raise RuntimeError("refine_warped: levels must be >= 1")
+        if not 1 <= int(max_views) <= 32:
+            raise RuntimeError("refine_warped: max_views must be in 1..32")
+        H = self.refine_hypotheses(kd, ka)
+        ncc = self.score_warped(c, nrm, ref, min_ncc, wid, min_cos, want_ncc=True)[4]
+        views = self.refine_view_lists(ncc, min_ncc, int(max_views))
+        dstep = self.refine_depth_steps(c, ref, depth_px)
+        dev = torch.device(f"cuda:{self.device}")
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        # a torch side stream of this context carries the whole chain (the
+        # handle of torch's default stream is 0, which the C-ABI reads as "the
+        # context's own stream")
+        if self._refine_stream is None:
+            self._refine_stream = torch.cuda.Stream(dev)
+        st = self._refine_stream
+        with torch.cuda.stream(st):
+            cur = [torch.from_numpy(c).to(dev), torch.from_numpy(nrm).to(dev)]
+            nxt = [torch.empty((n, 3), **f64), torch.empty((n, 3), **f64)]
+            t_ref, t_views, t_dstep = (torch.from_numpy(x).to(dev) for x in (ref, views, dstep))
+            best = torch.empty((levels, n), **i32)
+            sbest = torch.empty(n, **f64)
+            first = torch.empty((n, H), **f64)
+            for lev in range(levels):
+                self.refine_warped_level_device(cur[0], cur[1], t_ref, t_views, t_dstep, nxt[0], nxt[1], best[lev],
+                                                sbest, first if lev == 0 else None, wid, min_cos, kd, ka, astep,
+                                                2.0 ** -lev, stream=st.cuda_stream)
+                cur, nxt = nxt, cur
+            xy = torch.empty((n, 2), **f64)
+            mask = torch.empty((n, self.words), dtype=torch.int64, device=dev)
+            count = torch.empty(n, **i32)
+            avg = torch.empty(n, **f64)
+            self.score_warped_device(cur[0], cur[1], t_ref, xy, mask, count, avg, None, min_ncc, wid, min_cos,
+                                     stream=st.cuda_stream)
+            info = {"views": views, "best": best.cpu().numpy(),
+                    "score_first": first[:, (H - 1) // 2].cpu().numpy(), "score_last": sbest.cpu().numpy()}
+            out = (cur[0].cpu().numpy(), cur[1].cpu().numpy(),
+                   (xy.cpu().numpy(), mask.cpu().numpy().view(np.uint64), count.cpu().numpy(), avg.cpu().numpy()),
+                   info)
+        st.synchronize()
+        return out
 
     def pack_accepted(self, offset, count, mask, vlb, out, stream=None, c=None):
         """mvs_pack_accepted: the accepted candidates (count >= vlb) of a scored

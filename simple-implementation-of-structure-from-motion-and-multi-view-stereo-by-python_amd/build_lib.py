@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvs_amd.so")
 STAMPS_LIB = os.path.join(HERE, "libmvs_amd_stamps.so")   # diagnostic build (-DMVS_STAMPS)
 ASAN_LIB = os.path.join(HERE, "libmvs_amd_asan.so")       # host code under ASan + UBSan (tools/asan_cpu.sh)
-SOURCES = ["mvs_kernels.hip", "mvs_score_tab.hip", "mvs_warp.hip", "sfm_kernels.hip", "mvs_engine.cpp"]
+SOURCES = ["mvs_kernels.hip", "mvs_score_tab.hip", "mvs_warp.hip", "mvs_refine.hip", "sfm_kernels.hip", "mvs_engine.cpp"]
 HEADERS = ["mvs_internal.h", "mvs_device.h", "mvs_mma.h", os.path.join("..", "..", "include", "mvs_amd.h")]
 OBJDIR = os.path.join(HERE, "build")   # per-source objects (git- and gpurun-ignored)
 ARCH = os.environ.get("MVS_OFFLOAD_ARCH", "gfx950")

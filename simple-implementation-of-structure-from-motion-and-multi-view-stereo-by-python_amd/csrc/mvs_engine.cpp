@@ -311,6 +311,10 @@ struct mvs_ctx {
     DevBuf<double> w_in, w_out, w_ncc;
     DevBuf<int32_t> w_ref, w_count;
     DevBuf<uint64_t> w_mask;
+    // mvs_refine_warped's host-pointer buffers: [c, nrm, dstep], [c_out,
+    // nrm_out, score_best], [ref, best, views], scores (its own again)
+    DevBuf<double> r_in, r_out, r_scores;
+    DevBuf<int32_t> r_int;
     // tiled scorer scratch
     DevBuf<int32_t> t_tiles, t_cand;
     // mvs_pack_accepted: the pack's row counter and chunk ticket (k_acc_pack
@@ -1709,6 +1713,126 @@ int mvs_score_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm
         HIPCHK(hipMemcpyAsync(count, ctx->w_count.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (avg) HIPCHK(hipMemcpyAsync(avg, d_avg, n * sizeof(double), hipMemcpyDeviceToHost, s));
         if (ncc) HIPCHK(hipMemcpyAsync(ncc, ctx->w_ncc.p, n * V * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// argument checks shared by the two entry points of the refinement level
+static int refine_check(mvs_ctx* ctx, int64_t n, bool ptrs_ok, int tv, int wid, double min_cos, int kd, int ka,
+                        double astep, double step_scale) {
+    if (n < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: n < 0"});
+    if (n > ((int64_t)1 << 31)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: n above 2^31"});
+    if (wid < 1 || wid > MVS_MAX_WID) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: wid must be in 1..5"});
+    if (!(min_cos >= 0.0 && min_cos < 1.0))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: min_cos must be in [0, 1)"});
+    if (tv < 1 || tv > 32) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: tv must be in 1..32"});
+    if (kd < 0 || kd > 3) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: kd must be in 0..3"});
+    if (ka < 0 || ka > 2) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: ka must be in 0..2"});
+    if (!(step_scale > 0.0) || !std::isfinite(step_scale))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: step_scale must be > 0"});
+    if (!(astep >= 0.0) || !((double)ka * astep * step_scale <= 1.2))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: ka * astep * step_scale must be in [0, 1.2]"});
+    if (n > 0 && !ptrs_ok)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: null pointer (only scores may be NULL)"});
+    return 0;
+}
+
+static void refine_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                          const int32_t* d_views, int tv, const double* d_dstep, int wid, double min_cos, int kd,
+                          int ka, double astep, double step_scale, double* d_c_out, double* d_nrm_out,
+                          int32_t* d_best, double* d_score_best, double* d_scores, hipStream_t s) {
+    RefineArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.views = d_views;
+    a.dstep = d_dstep;
+    a.tv = tv;
+    a.kd = kd;
+    a.ka = ka;
+    a.min_cos = min_cos;
+    a.step_scale = step_scale;
+    // the grid's tangents from the host's libm (what a caller's own tan() gives)
+    const double alpha = astep * step_scale;
+    for (int i = -ka; i <= ka; ++i) a.tans[i + ka] = std::tan((double)i * alpha);
+    a.c_out = d_c_out;
+    a.nrm_out = d_nrm_out;
+    a.best = d_best;
+    a.score_best = d_score_best;
+    a.scores = d_scores;
+    if (mvs_launch_refine_warp(&ctx->sc, &a, wid, s) != 0) throw Fail{MVS_E_HIP, "refine_warp launch failed"};
+}
+
+int mvs_refine_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                             const int32_t* d_views, int tv, const double* d_dstep, int wid, double min_cos, int kd,
+                             int ka, double astep, double step_scale, double* d_c_out, double* d_nrm_out,
+                             int32_t* d_best, double* d_score_best, double* d_scores, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = refine_check(ctx, n, d_c && d_nrm && d_ref && d_views && d_dstep && d_c_out && d_nrm_out && d_best &&
+                                          d_score_best, tv, wid, min_cos, kd, ka, astep, step_scale))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        refine_launch(ctx, n, d_c, d_nrm, d_ref, d_views, tv, d_dstep, wid, min_cos, kd, ka, astep, step_scale,
+                      d_c_out, d_nrm_out, d_best, d_score_best, d_scores, s);
+        return 0;
+    });
+}
+
+int mvs_refine_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                      const int32_t* views, int tv, const double* dstep, int wid, double min_cos, int kd, int ka,
+                      double astep, double step_scale, double* c_out, double* nrm_out, int32_t* best,
+                      double* score_best, double* scores) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = refine_check(ctx, n, c && nrm && ref && views && dstep && c_out && nrm_out && best && score_best,
+                              tv, wid, min_cos, kd, ka, astep, step_scale))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        const int V = ctx->V;
+        for (int64_t i = 0; i < n; ++i) {
+            if (ref[i] < 0 || ref[i] >= V) throw Fail{MVS_E_ARG, "mvs_refine_warped: ref view out of range"};
+            const int32_t* l = views + i * tv;
+            bool ended = false;
+            for (int j = 0; j < tv; ++j) {
+                if (l[j] < -1 || l[j] >= V) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view out of range"};
+                if (l[j] < 0) { ended = true; continue; }
+                if (ended) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view after a -1"};
+                if (l[j] == ref[i]) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view equal to ref"};
+                for (int k = 0; k < j; ++k)
+                    if (l[k] == l[j]) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view repeated"};
+            }
+        }
+        hipStream_t s = ctx->stream;
+        const int A = 2 * ka + 1;
+        const int64_t H = (int64_t)(2 * kd + 1) * A * A;
+        // buffers of this call alone (none of the scorers' or the warped test's)
+        ctx->r_in.ensure(n * 7); ctx->r_out.ensure(n * 7); ctx->r_int.ensure(n * (tv + 2));
+        if (scores) ctx->r_scores.ensure(n * H);
+        double* d_c = ctx->r_in.p;
+        double* d_nrm = d_c + n * 3;
+        double* d_dstep = d_c + n * 6;
+        double* d_co = ctx->r_out.p;
+        double* d_no = d_co + n * 3;
+        double* d_sb = d_co + n * 6;
+        int32_t* d_ref = ctx->r_int.p;
+        int32_t* d_best = d_ref + n;
+        int32_t* d_views = d_ref + 2 * n;
+        HIPCHK(hipMemcpyAsync(d_c, c, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_nrm, nrm, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_dstep, dstep, n * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_ref, ref, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_views, views, n * tv * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        refine_launch(ctx, n, d_c, d_nrm, d_ref, d_views, tv, d_dstep, wid, min_cos, kd, ka, astep, step_scale, d_co,
+                      d_no, d_best, d_sb, scores ? ctx->r_scores.p : nullptr, s);
+        HIPCHK(hipMemcpyAsync(c_out, d_co, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(nrm_out, d_no, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(score_best, d_sb, n * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(best, d_best, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->r_scores.p, n * H * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     });

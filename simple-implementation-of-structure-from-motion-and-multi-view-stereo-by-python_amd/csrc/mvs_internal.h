@@ -73,6 +73,25 @@ struct WarpArgs {
     double* ncc;          // n*V (may be null): nan for ref, culled and failed views
 };
 
+// Inputs/outputs of one level of the depth and normal refinement
+// (k_refine_warp, mvs_refine.hip; device pointers).
+struct RefineArgs {
+    int64_t n;
+    const double* c;       // n*3 patch centres
+    const double* nrm;     // n*3 unit normals (towards the cameras; not checked)
+    const int32_t* ref;    // n
+    const int32_t* views;  // n*tv view lists, unused slots -1 at the end
+    const double* dstep;   // n depth steps (world units)
+    int tv, kd, ka;
+    double min_cos, step_scale;
+    double tans[5];        // tan(i astep step_scale), i = -ka..ka, from the host's libm
+    double* c_out;         // n*3
+    double* nrm_out;       // n*3
+    int32_t* best;         // n chosen hypothesis, -1 = none
+    double* score_best;    // n
+    double* scores;        // n*H (may be null), H = (2 kd + 1)(2 ka + 1)^2
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -253,6 +272,9 @@ int mvs_launch_score(const SceneDev* sc, const ScoreArgs* a, int wid, hipStream_
 // plane-warped photo test (k_score_warp, mvs_warp.hip): one wave per
 // candidate, no scratch; wid in 1..5
 int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStream_t s);
+// one level of the refinement against that test (k_refine_warp,
+// mvs_refine.hip): one wave per candidate, lane = (hypothesis, list view)
+int mvs_launch_refine_warp(const SceneDev* sc, const RefineArgs* a, int wid, hipStream_t s);
 // tiled scorer: k_bin (tile buckets, then the work items), k_score_mma or k_score_mma_v
 // (timed by ev0/ev1), k_score_fix
 int mvs_launch_score_tiled(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, int wid,

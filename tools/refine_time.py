@@ -1,0 +1,173 @@
+"""Timing of one level of the depth and normal refinement
+(mvs_refine_warped_device, kernel k_refine_warp) on dinoRing: 2^14
+synthetic.candidates, normal = unit vector from the centre to the reference
+camera, view lists from refine_warped's rule (min_ncc 0.7, 8 views) at min_cos
+0.3, the 45-hypothesis grid (kd 2, ka 1, 8 degrees, depth step 1.5 px), at
+wid 5 and wid 3.  Each wid runs in a child process of its own under a time
+limit; the calls are timed with device events on one stream after warm-up,
+over several windows (the median window is reported, with the fastest and
+slowest).  Prints one JSON line:
+
+  us_per_level, pairs_per_s ((hypothesis, list view) pairs), samples_per_s,
+  mean_T, lane_use (sum |T| / sum S over the patches with a list) per wid,
+
+and the baseline timed in the same process: the same H n hypotheses expanded
+into H n candidates of score_warped_device with ncc output -- what a caller
+had to do before this call existed -- with the ratio baseline / level.
+
+A pair is counted for every hypothesis of a patch that passes the candidate
+test (the kernel skips the samples of a pair that fails its facing test, so
+samples_per_s is an upper bound by that share).
+
+usage: python tools/refine_time.py [--n 16384] [--calls 20] [--windows 5] [--limit 300]
+"""
+import argparse
+import importlib
+import json
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "simple-implementation-of-structure-from-motion-and-multi-view-stereo-by-python_amd"
+DATA = os.path.join(REPO, "data", "dinoRing")
+KD, KA, ASTEP, MAX_VIEWS, MIN_NCC = 2, 1, math.radians(8), 8, 0.7
+
+
+def expand(c, nrm, ref, O, dstep):
+    """The H hypotheses of every patch as (n H, 3) centres and normals (the
+    grid of the definition, vectorised)."""
+    n = len(ref)
+    e = c - O[ref]
+    u = e / np.linalg.norm(e, axis=1, keepdims=True)
+    axis = np.zeros((n, 3))
+    axis[np.arange(n), np.argmin(np.abs(nrm), axis=1)] = 1.0
+    e1 = np.cross(nrm, axis)
+    e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+    e2 = np.cross(nrm, e1)
+    cs, ns = [], []
+    for k in range(-KD, KD + 1):
+        ck = c + (k * dstep)[:, None] * u
+        for j in range(-KA, KA + 1):
+            for i in range(-KA, KA + 1):
+                v = nrm + math.tan(i * ASTEP) * e1 + math.tan(j * ASTEP) * e2
+                cs.append(ck)
+                ns.append(v / np.linalg.norm(v, axis=1, keepdims=True))
+    H = len(cs)
+    return (np.ascontiguousarray(np.stack(cs, 1).reshape(n * H, 3)),
+            np.ascontiguousarray(np.stack(ns, 1).reshape(n * H, 3)), np.repeat(ref, H).astype(np.int32), H)
+
+
+def timed(torch, st, call, calls, windows):
+    for _ in range(3):
+        call()
+    st.synchronize()
+    us = []
+    for _ in range(windows):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(calls):
+            call()
+        e1.record(st)
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3 / calls)
+    us.sort()
+    return us
+
+
+def child(a):
+    import torch
+    assert torch.cuda.is_available(), "refine_time needs the GPU"
+    mvs = importlib.import_module(PKG)
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    from make_seeds import load_dino
+    imgs, K, R, t = load_dino(DATA)
+    rgb = np.stack(imgs)
+    c, ref = mvs.synthetic.candidates(a.n, K, R, t, seed=0)
+    dev = torch.device("cuda:0")
+    n, wid = a.n, a.wid
+    with mvs.MvsContext(rgb, K, R, t, device=0) as ctx:
+        O = -np.einsum("vji,vj->vi", ctx.rproj(), t.reshape(-1, 3))
+        nrm = O[ref] - c
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        _, _, count, _, ncc = ctx.score_warped(c, nrm, ref, MIN_NCC, wid, a.min_cos, want_ncc=True)
+        valid = ~np.all(np.isnan(ncc), axis=1) | (count > 0)     # the candidate test passed (some view was scored)
+        views = ctx.refine_view_lists(ncc, MIN_NCC, MAX_VIEWS)
+        del ncc
+        dstep = ctx.refine_depth_steps(c, ref, 1.5)
+        T = (views >= 0).sum(1)
+        S = np.array([1 << int(x - 1).bit_length() if x > 0 else 0 for x in T])
+        ec, en, er, H = expand(c, nrm, ref, O, dstep)
+        st = torch.cuda.Stream(dev)
+        with torch.cuda.stream(st):
+            tc, tn, tr, tv, td = (torch.from_numpy(v).to(dev) for v in (c, nrm, ref, views, dstep))
+            co, no = torch.empty_like(tc), torch.empty_like(tn)
+            best = torch.empty(n, dtype=torch.int32, device=dev)
+            sb = torch.empty(n, dtype=torch.float64, device=dev)
+
+            def level():
+                ctx.refine_warped_level_device(tc, tn, tr, tv, td, co, no, best, sb, None, wid, a.min_cos, KD, KA,
+                                               ASTEP, 1.0, stream=st.cuda_stream)
+            us = timed(torch, st, level, a.calls, a.windows)
+            moved = int((best != (H - 1) // 2).logical_and(best >= 0).sum().item())
+            chosen = int((best >= 0).sum().item())
+            # the baseline: every hypothesis as a candidate of the warped test, ncc out
+            m = n * H
+            bc, bn, br = (torch.from_numpy(v).to(dev) for v in (ec, en, er))
+            xy = torch.empty((m, 2), dtype=torch.float64, device=dev)
+            mask = torch.empty((m, ctx.words), dtype=torch.int64, device=dev)
+            cnt = torch.empty(m, dtype=torch.int32, device=dev)
+            out = torch.empty((m, ctx.V), dtype=torch.float64, device=dev)
+
+            def baseline():
+                ctx.score_warped_device(bc, bn, br, xy, mask, cnt, None, out, MIN_NCC, wid, a.min_cos,
+                                        stream=st.cuda_stream)
+            ub = timed(torch, st, baseline, max(a.calls // 4, 2), a.windows)
+    med, bmed = us[len(us) // 2], ub[len(ub) // 2]
+    N = (2 * wid + 1) ** 2
+    pairs = int(T[valid].sum()) * H
+    samples = pairs * N
+    print(json.dumps({"wid": wid, "n": n, "hypotheses": H, "calls_per_window": a.calls, "windows": a.windows,
+                      "us_per_level": round(med, 2), "us_min": round(us[0], 2), "us_max": round(us[-1], 2),
+                      "patches_with_a_list": int((T > 0).sum()), "patches_with_a_choice": chosen,
+                      "patches_moved": moved, "mean_T": float(T[T > 0].mean()),
+                      "lane_use": float(T.sum() / max(S.sum(), 1)), "pairs": pairs, "samples": samples,
+                      "pairs_per_s": pairs / med * 1e6, "samples_per_s": samples / med * 1e6,
+                      "baseline_us": round(bmed, 2), "baseline_us_min": round(ub[0], 2),
+                      "baseline_us_max": round(ub[-1], 2), "baseline_over_level": bmed / med}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1 << 14)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--min-cos", type=float, default=0.3)
+    ap.add_argument("--limit", type=int, default=300, help="seconds allowed to each wid's process")
+    ap.add_argument("--wid", type=int, default=0, help="(child) the one wid to time")
+    a = ap.parse_args()
+    if a.wid:
+        sys.path.insert(0, REPO)
+        child(a)
+        return 0
+    out = {"kernel": "k_refine_warp", "scene": "dinoRing 48 x 640 x 480", "min_ncc": MIN_NCC, "min_cos": a.min_cos,
+           "kd": KD, "ka": KA, "astep_deg": 8, "depth_px": 1.5, "max_views": MAX_VIEWS}
+    for wid in (5, 3):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--wid", str(wid),
+               "--n", str(a.n), "--calls", str(a.calls), "--windows", str(a.windows), "--min-cos", str(a.min_cos)]
+        p = subprocess.run(cmd, capture_output=True, text=True)
+        if p.returncode != 0:
+            # nothing more is started on the GPU after a step that failed
+            sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+            print(json.dumps({"error": f"wid {wid} exited with {p.returncode}", **out}))
+            return 1
+        out[f"wid{wid}"] = json.loads(p.stdout.strip().splitlines()[-1])
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

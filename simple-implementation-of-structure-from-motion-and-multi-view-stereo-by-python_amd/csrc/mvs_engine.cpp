@@ -2265,7 +2265,11 @@ int mvs_match_two_sided(mvs_ctx* ctx, int view_a, const int32_t* pts_a, int64_t 
                     throw Fail{MVS_E_ARG, "point outside getDescFeatures' bounds"};
             }
         }
-        if (n_a == 0) return 0;
+        if (n_a == 0) {
+            // no A row: every B row's dist row is empty, so no match
+            if (best21) std::fill(best21, best21 + n_b, -1);
+            return 0;
+        }
         const int npx = (2 * wid + 1) * (2 * wid + 1);
         constexpr int DW = 32;   // descriptor dwords (kDescWords)
         const int64_t n = n_a + n_b;

@@ -208,8 +208,11 @@ DEV uint32_t desc_byte(const uint32_t* d, int p) { return (d[p >> 2] >> (8 * (p 
 // Match(desc1, desc2, thr) (HarrisFeatures.py:15-37), one direction: one wave
 // per row i, lanes over j.  ncc from the exact integer moments (closed form);
 // a value within kGuard of thr is decided by the numpy-order ctNcc; best =
-// max ncc > thr with ties to the smallest j; candidates within 1e-12 of the
-// best are re-ranked on their numpy-order values.  -1: no ncc above thr.
+// max ncc > thr with ties to the smallest j; every candidate within 1e-12 of
+// the best is re-ranked on its numpy-order value (equal integer moments give
+// bit-identical closed forms whose ctNcc differ in the last ulp).  A lane keeps
+// its two largest values and the largest one it let go, so a row without
+// three near ties in one lane takes no extra ctNcc.  -1: no ncc above thr.
 __global__ __launch_bounds__(256) void k_match_rows(
         const uint32_t* __restrict__ dA, const int32_t* __restrict__ SA, const int32_t* __restrict__ SSA,
         int64_t nA, const uint32_t* __restrict__ dB, const int32_t* __restrict__ SB,
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(256) void k_match_rows(
         (const __attribute__((address_space(4))) uint32_t*)(dA + i * kDescWords);
     const int64_t si = SA[i], ssi = SSA[i];
     const int64_t da = (int64_t)npx * ssi - si * si;
-    double v1 = -2.0, v2 = -2.0;
+    double v1 = -2.0, v2 = -2.0, v3 = -2.0;   // v3: the largest value that left the two slots
     int64_t j1 = -1, j2 = -1;
     auto exact = [&](int64_t j) {
         const uint32_t* a = dA + i * kDescWords;
@@ -229,30 +232,39 @@ __global__ __launch_bounds__(256) void k_match_rows(
         return exact_ncc_generic([&](int p) -> int { return (int)desc_byte(a, p); },
                                  [&](int p) -> int { return (int)desc_byte(b, p); }, npx);
     };
+    // candidate j's value; false: not a candidate (constant window, or not above thr)
+    auto value = [&](int64_t j, double& ncc) -> bool {
+        const uint4* pb = (const uint4*)(dB + j * kDescWords);
+        uint32_t sab = 0;
+#pragma unroll
+        for (int k4 = 0; k4 < kDescWords / 4; ++k4) {
+            const uint4 w = pb[k4];
+            sab = __builtin_amdgcn_udot4(di[4 * k4], w.x, sab, false);
+            sab = __builtin_amdgcn_udot4(di[4 * k4 + 1], w.y, sab, false);
+            sab = __builtin_amdgcn_udot4(di[4 * k4 + 2], w.z, sab, false);
+            sab = __builtin_amdgcn_udot4(di[4 * k4 + 3], w.w, sab, false);
+        }
+        const int64_t sj = SB[j], ssj = SSB[j];
+        const int64_t db = (int64_t)npx * ssj - sj * sj;
+        if (db <= 0) return false;                         // constant window: ncc is NaN
+        const int64_t num = (int64_t)npx * (int64_t)sab - si * sj;
+        ncc = (double)(npx * num) / ((double)(npx - 1) * sqrt((double)da * (double)db));
+        if (fabs(ncc - thr) <= kGuard) ncc = exact(j);
+        return ncc > thr;
+    };
     if (da > 0) {
         for (int64_t j = lane; j < nB; j += 64) {
-            const uint4* pb = (const uint4*)(dB + j * kDescWords);
-            uint32_t sab = 0;
-#pragma unroll
-            for (int k4 = 0; k4 < kDescWords / 4; ++k4) {
-                const uint4 w = pb[k4];
-                sab = __builtin_amdgcn_udot4(di[4 * k4], w.x, sab, false);
-                sab = __builtin_amdgcn_udot4(di[4 * k4 + 1], w.y, sab, false);
-                sab = __builtin_amdgcn_udot4(di[4 * k4 + 2], w.z, sab, false);
-                sab = __builtin_amdgcn_udot4(di[4 * k4 + 3], w.w, sab, false);
-            }
-            const int64_t sj = SB[j], ssj = SSB[j];
-            const int64_t db = (int64_t)npx * ssj - sj * sj;
-            if (db <= 0) continue;                         // constant window: ncc is NaN
-            const int64_t num = (int64_t)npx * (int64_t)sab - si * sj;
-            double ncc = (double)(npx * num) / ((double)(npx - 1) * sqrt((double)da * (double)db));
-            if (fabs(ncc - thr) <= kGuard) ncc = exact(j);
-            if (!(ncc > thr)) continue;
+            double ncc;
+            if (!value(j, ncc)) continue;
             if (ncc > v1) {
+                v3 = v2;
                 v2 = v1; j2 = j1;
                 v1 = ncc; j1 = j;
             } else if (ncc > v2) {
+                v3 = v2;
                 v2 = ncc; j2 = j;
+            } else {
+                v3 = fmax(v3, ncc);
             }
         }
     }
@@ -265,16 +277,29 @@ __global__ __launch_bounds__(256) void k_match_rows(
         if (ov > bv || (ov == bv && oj >= 0 && (bj < 0 || oj < bj))) { bv = ov; bj = oj; }
     }
     if (bj >= 0) {
-        // near ties: re-rank every lane's top two within 1e-12 of the best on
-        // their numpy-order ctNcc
+        // near ties: re-rank every candidate within 1e-12 of the best on its
+        // numpy-order ctNcc.  A lane's two slots hold them all unless the
+        // largest value that left the slots (v3 <= v2 <= v1) is in the band
+        // too: such a lane walks its candidates again (ascending j, so equal
+        // values keep the smallest j).
         const bool c1 = j1 >= 0 && fabs(v1 - bv) <= 1e-12, c2 = j2 >= 0 && fabs(v2 - bv) <= 1e-12;
+        const bool c3 = c2 && fabs(v3 - bv) <= 1e-12;
         if (__popcll(__ballot(c1)) + __popcll(__ballot(c2)) > 1) {
             double ev = -2.0;
             int64_t ej = -1;
-            if (c1) { ev = exact(j1); ej = j1; }
-            if (c2) {
-                const double e2 = exact(j2);
-                if (e2 > ev || (e2 == ev && j2 < ej)) { ev = e2; ej = j2; }
+            if (c3) {
+                for (int64_t j = lane; j < nB; j += 64) {
+                    double ncc;
+                    if (!value(j, ncc) || fabs(ncc - bv) > 1e-12) continue;
+                    const double e = exact(j);
+                    if (e > ev) { ev = e; ej = j; }
+                }
+            } else {
+                if (c1) { ev = exact(j1); ej = j1; }
+                if (c2) {
+                    const double e2 = exact(j2);
+                    if (e2 > ev || (e2 == ev && j2 < ej)) { ev = e2; ej = j2; }
+                }
             }
             for (int off = 32; off > 0; off >>= 1) {
                 const double ov = __shfl_xor(ev, off, 64);

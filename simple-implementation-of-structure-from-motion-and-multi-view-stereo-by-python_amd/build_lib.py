@@ -13,17 +13,26 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmvs_amd.so")
 STAMPS_LIB = os.path.join(HERE, "libmvs_amd_stamps.so")   # diagnostic build (-DMVS_STAMPS)
 ASAN_LIB = os.path.join(HERE, "libmvs_amd_asan.so")       # host code under ASan + UBSan (tools/asan_cpu.sh)
-SOURCES = ["mvs_kernels.hip", "mvs_score_tab.hip", "mvs_warp.hip", "mvs_refine.hip", "sfm_kernels.hip", "mvs_engine.cpp"]
-HEADERS = ["mvs_internal.h", "mvs_device.h", "mvs_mma.h", os.path.join("..", "..", "include", "mvs_amd.h")]
+# the one list of sources (tools/build_variant.sh reads it through --sources), the slowest to compile first
+SOURCES = ["mvs_score_tab.hip", "mvs_score_mma.hip", "mvs_score_mma_v.hip", "mvs_sort.hip", "mvs_kernels.hip",
+           "mvs_bin.hip", "mvs_exchange.hip", "mvs_warp.hip", "mvs_refine.hip", "sfm_kernels.hip", "mvs_engine.cpp"]
+
+# every header a source may include, found, not listed: csrc/*.h and the public header (paths from csrc/)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "mvs_amd.h")]
 OBJDIR = os.path.join(HERE, "build")   # per-source objects (git- and gpurun-ignored)
 ARCH = os.environ.get("MVS_OFFLOAD_ARCH", "gfx950")
+
+
+def inputs():
+    """Every file the library is built from (needs_build() compares their times with the library's)."""
+    return [os.path.normpath(os.path.join(CSRC, f)) for f in SOURCES + HEADERS]
 
 
 def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    return any(os.path.getmtime(f) > t for f in inputs())
 
 
 def build(force=False, verbose=False, stamps=False, asan=False):
@@ -95,5 +104,8 @@ def check_undefined(path):
 
 
 if __name__ == "__main__":
+    if "--sources" in sys.argv:
+        print(" ".join(SOURCES))
+        sys.exit(0)
     print(build(force="--force" in sys.argv, verbose=True, stamps="--stamps" in sys.argv,
                 asan="--asan" in sys.argv))

@@ -1,13 +1,83 @@
-// Device helpers shared by the HIP translation units (mvs_kernels.hip,
-// sfm_kernels.hip): the reference's projection, window bounds and ctNcc in
-// numpy's operation order.  Compiled with -ffp-contract=off: every fused
-// product is written as fma() (numpy/OpenBLAS 3-element dot products).
+// Helpers shared by every HIP unit (mvs_*.hip, sfm_kernels.hip): the
+// reference's projection, window bounds and ctNcc in numpy's operation order,
+// wave sums, fences and barriers, the launchers' dispatch on the window half-width.
+// -ffp-contract=off: every fused product is written as fma() (numpy/OpenBLAS).
 #pragma once
+#include <type_traits>
+
 #include "mvs_internal.h"
 
 #define DEV __device__ __forceinline__
 
 namespace {
+
+// Sum over the wave's 64 lanes (all active), on every lane: xor 32, 16, ... 1.
+DEV int wave_sum(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+DEV double wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// x through an opaque copy: what is computed from it is not hoisted out of loops into long-lived registers
+DEV int opaque(int x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// Workgroup barrier for LDS traffic: every wave's LDS operations are complete first; outstanding
+// global loads and LDS-DMA are not waited for (the fence of __syncthreads would: vmcnt(0)).
+DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// a wave's own LDS rows: writes above, reads below, in program order (no workgroup barrier)
+DEV void wave_lds_publish() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// 1 / w from v_rcp_f64 and two Newton steps (k_score_warp, k_refine_warp):
+// within about an ulp, NOT project()'s correctly rounded IEEE quotient (a dozen
+// instructions more, twice per sample).  Enough there: it feeds samples of the
+// warped test alone, not the xy output, and an ulp of 1/z moves a sample by
+// ~1e-13 px against the 1.5e-12 px that the tests' tolerance is built on.
+DEV double recip(double w) {
+    double r = __builtin_amdgcn_rcp(w);
+    r = fma(fma(-w, r, 1.0), r, r);
+    r = fma(fma(-w, r, 1.0), r, r);
+    return r;
+}
+
+// f(integral_constant<int, wid>) for a window half-width wid in 1..MVS_MAX_WID,
+// else the caller's "bad wid" code.
+template <class R, class F>
+inline R dispatch_wid(int wid, R bad, F&& f) {
+    switch (wid) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        default: return bad;
+    }
+}
+static_assert(MVS_MAX_WID == 5, "dispatch_wid lists the window half-widths");
+
+// Records ev0 on construction and ev1 on destruction (when given): brackets one kernel launch on stream s.
+struct TimedLaunch {
+    hipStream_t s;
+    hipEvent_t e1;
+    TimedLaunch(hipStream_t s_, hipEvent_t e0, hipEvent_t e1_) : s(s_), e1(e1_) {
+        if (e0) (void)hipEventRecord(e0, s);
+    }
+    ~TimedLaunch() {
+        if (e1) (void)hipEventRecord(e1, s);
+    }
+};
 
 // |ncc - thr| band (absolute) inside which a closed-form value is replaced by
 // the numpy-order ctNcc before the decision

@@ -1,5 +1,5 @@
-// Internal declarations shared by the HIP kernels (mvs_kernels.hip,
-// sfm_kernels.hip) and the host engine (mvs_engine.cpp).  Not part of the
+// Internal declarations shared by the HIP units (mvs_*.hip, sfm_kernels.hip)
+// and the host engine (mvs_engine.cpp).  Not part of the
 // public C-ABI (include/mvs_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -275,8 +275,9 @@ int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStr
 // one level of the refinement against that test (k_refine_warp,
 // mvs_refine.hip): one wave per candidate, lane = (hypothesis, list view)
 int mvs_launch_refine_warp(const SceneDev* sc, const RefineArgs* a, int wid, hipStream_t s);
-// tiled scorer: k_bin (tile buckets, then the work items), k_score_mma or k_score_mma_v
-// (timed by ev0/ev1), k_score_fix
+// tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
+// scorer of the scene's shape through its launcher below (timed by ev0/ev1),
+// k_score_fix
 int mvs_launch_score_tiled(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, int wid,
                            const MomentsDev* mt, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 // 1 if mvs_launch_score_tiled takes the runs path for this batch (k_score_tab,
@@ -289,8 +290,16 @@ int mvs_launch_moments(const SceneDev* sc, const MomentsDev* mt, hipStream_t s);
 // (V > 64: k_score_mma_v takes the tables through mvs_launch_score_tiled)
 int mvs_launch_score_tab(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, const MomentsDev* mt,
                          hipStream_t s);
-// dynamic LDS bytes of k_score_mma (0 if the configuration is unsupported)
+// the tiled launcher's other scorers and its last kernel, each in its own
+// unit; k_bin has run.  k_score_mma (V <= 64, no tables), k_score_mma_v
+// (V > 64, mt may be null), k_score_fix (the fix list by the direct path)
+int mvs_launch_score_mma(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, int wid, hipStream_t s);
+int mvs_launch_score_mma_v(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, const MomentsDev* mt,
+                           int wid, hipStream_t s);
+int mvs_launch_score_fix(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, int wid, hipStream_t s);
+// dynamic LDS bytes of k_score_mma (0: unsupported); V > 64: all LDS of k_score_mma_v, from its unit
 size_t mvs_mma_lds_bytes(int V, int wid);
+size_t mvs_mma_v_lds_bytes(int wid);
 // name of the kernel mvs_launch_score / mvs_launch_score_tiled time for (V, wid)
 const char* mvs_timed_kernel_name(int V, int wid, int tiled);
 // patch_expansion children, one wave each: geometry + direct photo test +

@@ -1,13 +1,35 @@
-// Device helpers of the tiled matrix-core scorers (k_score_mma, k_score_mma_v
-// in mvs_kernels.hip; k_score_tab in mvs_score_tab.hip): the tile geometry,
-// the i8 MFMA operand masks, EXEC-masked binary64 accumulation, lane moves
-// and reductions.  gfx950 only.
+// Helpers of the tiled matrix-core scorers (k_score_mma in mvs_score_mma.hip,
+// k_score_mma_v in mvs_score_mma_v.hip, k_score_tab in mvs_score_tab.hip) and
+// of the unit that bins for them (mvs_bin.hip): the tile geometry and work
+// items, the i8 MFMA operand masks, EXEC-masked binary64 accumulation, lane
+// moves and reductions.  gfx950 only.
 #pragma once
+#include <atomic>
 #include <utility>
 
 #include "mvs_device.h"
 
 namespace {
+
+constexpr int kMmaGrid = 256;         // the scorers' workgroups: one per CU; the queue balances
+constexpr int kMmaThreads = 1024, kMmaWaves = kMmaThreads / 64;
+constexpr int kGroupViews = MVS_GROUP_VIEWS;   // views per view group (V > 64): one mask word
+constexpr int kMmaChunk = MVS_MMA_CHUNK;       // candidates per work item, V <= 64 (<= 1024: the scorers' lists)
+constexpr int kGroupChunk = MVS_GROUP_CHUNK;   // candidates per work item, V > 64 (reference windows staged)
+constexpr int kSortBins = MVS_TILE_H / 2;   // k_score_mma sorts an item's candidates by row pair
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, set once per device
+// (a per-device bit per kernel; racing first launches from two threads may
+// both set it, which is harmless)
+inline int set_dyn_lds_once(const void* f, std::atomic<uint64_t>& done, int lds) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    const uint64_t bit = dev < 64 ? (1ull << dev) : 0ull;
+    if (bit && (done.load(std::memory_order_acquire) & bit)) return 0;
+    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
+    done.fetch_or(bit, std::memory_order_release);
+    return 0;
+}
 
 // Binary64 DPP move (both halves), bound_ctrl: every source lane exists.
 template <int CTRL>
@@ -51,13 +73,6 @@ struct MmaGeom {
     static_assert(C0 >= 0 && C0 + MVS_TILE_W - 1 + NB <= 32, "window must fit the 32 region columns");
     static_assert(ROWS % 2 == 0, "K-steps take two rows");
 };
-
-// x through an opaque copy: what is computed from it is computed where it is
-// used, not hoisted out of loops into long-lived registers
-DEV int opaque(int x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 
 // Band queues of a persistent scorer: work items [0, n) in nb contiguous
 // bands, band x's head at heads[32 x]; the first skip(x) items of band x are
@@ -166,11 +181,5 @@ DEV int4 item_desc(const TiledArgs& t, const int4* __restrict__ items, const Ite
     const int cnt = min(t.tile_count[it.x * kTcStride], t.cap);
     return make_int4(it.x, it.x * t.cap + it.y * t.chunk, min(cnt - it.y * t.chunk, t.chunk), 0);
 }
-
-// Workgroup barrier for LDS traffic: every wave's LDS operations are complete
-// first; outstanding global loads and LDS-DMA are not waited for (the fence of
-// __syncthreads would wait for them: vmcnt(0)).
-DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 
 }  // namespace

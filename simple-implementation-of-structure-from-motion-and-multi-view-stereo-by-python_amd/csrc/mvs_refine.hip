@@ -34,20 +34,6 @@ struct RaySample {
     double a;            // reference gray value - 128
 };
 
-DEV int wave_sum_i32(int x) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
-// 1 / w from v_rcp_f64 and two Newton steps (k_score_warp's: within about an
-// ulp, which moves a sample by ~1e-13 px).
-DEV double recip(double w) {
-    double r = __builtin_amdgcn_rcp(w);
-    r = fma(fma(-w, r, 1.0), r, r);
-    r = fma(fma(-w, r, 1.0), r, r);
-    return r;
-}
-
 // The candidate's frame of the grid: u along the reference ray, e1 and e2 the
 // tangent basis of the definition.
 struct GridFrame {
@@ -178,8 +164,8 @@ __global__ __launch_bounds__(256) void k_refine_warp(const SceneDev sc, const Re
             sa += gq;
             saa += gq * gq;
         }
-        sa = wave_sum_i32(sa);
-        saa = wave_sum_i32(saa);
+        sa = wave_sum(sa);
+        saa = wave_sum(saa);
         Sa = (double)sa;
         Da = (double)(N * saa - sa * sa);   // exact: |.| < 2^31 at N <= 121, |g| <= 128
         valid = Da > 0.0;
@@ -197,10 +183,7 @@ __global__ __launch_bounds__(256) void k_refine_warp(const SceneDev sc, const Re
         }
         return;
     }
-    // the wave's own LDS rows: writes above, reads below, in program order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_publish();
 
     grid_frame(g, Or);
 
@@ -335,13 +318,8 @@ __global__ __launch_bounds__(256) void k_refine_warp(const SceneDev sc, const Re
 extern "C" int mvs_launch_refine_warp(const SceneDev* sc, const RefineArgs* a, int wid, hipStream_t s) {
     if (a->n <= 0) return 0;
     const dim3 grid((unsigned)((a->n + 3) / 4)), block(256);
-    switch (wid) {
-        case 1: hipLaunchKernelGGL(k_refine_warp<1>, grid, block, 0, s, *sc, *a); break;
-        case 2: hipLaunchKernelGGL(k_refine_warp<2>, grid, block, 0, s, *sc, *a); break;
-        case 3: hipLaunchKernelGGL(k_refine_warp<3>, grid, block, 0, s, *sc, *a); break;
-        case 4: hipLaunchKernelGGL(k_refine_warp<4>, grid, block, 0, s, *sc, *a); break;
-        case 5: hipLaunchKernelGGL(k_refine_warp<5>, grid, block, 0, s, *sc, *a); break;
-        default: return -1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch_wid(wid, -1, [&](auto w) {
+        hipLaunchKernelGGL(k_refine_warp<decltype(w)::value>, grid, block, 0, s, *sc, *a);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }

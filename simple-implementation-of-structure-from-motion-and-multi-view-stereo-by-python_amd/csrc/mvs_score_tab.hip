@@ -197,12 +197,6 @@ __device__ unsigned long long g_stamps_tab[1024 * 16];
 // issue by fewer waves or later, 10 waves, tail-split items, one workgroup
 // per CU, ...) are in DESIGN.md 4.1 with their logs under profiles/r05/; the
 // code of each is in the git history (round 5), not in this file.
-DEV int wave_sum(int x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
 // inclusive scan of x over the wave's 64 lanes (all active) by DPP adds: row
 // shifts by 1, 2, 4, 8, then lane 15 of rows 0 and 2 into rows 1 and 3 and
 // lane 31 into rows 2 and 3 -- no LDS round trips (a shuffle takes one each)
@@ -965,17 +959,11 @@ extern "C" int mvs_launch_moments(const SceneDev* sc, const MomentsDev* mt, hipS
     if (mt->VP != (sc->V > 64 ? 64 * ((sc->V + 63) / 64) : 16 * ((sc->V + 15) / 16))) return -3;
     const dim3 grid((unsigned)((sc->W + kMomW - 1) / kMomW), (unsigned)((sc->H + kMomH - 1) / kMomH),
                     (unsigned)(mt->VP / kMomV));
-#define MVS_MOM(W_) (dtab ? (const void*)k_moments<W_, true> : (const void*)k_moments<W_, false>)
-    const void* f = nullptr;
-    switch (mt->wid) {
-        case 1: f = MVS_MOM(1); break;
-        case 2: f = MVS_MOM(2); break;
-        case 3: f = MVS_MOM(3); break;
-        case 4: f = MVS_MOM(4); break;
-        case 5: f = MVS_MOM(5); break;
-        default: return -2;
-    }
-#undef MVS_MOM
+    const void* f = dispatch_wid(mt->wid, (const void*)nullptr, [&](auto w) {
+        constexpr int WID = decltype(w)::value;
+        return dtab ? (const void*)k_moments<WID, true> : (const void*)k_moments<WID, false>;
+    });
+    if (!f) return -2;
     const SceneDev scv = *sc;
     const MomentsDev mtv = *mt;
     void* args[] = {(void*)&scv, (void*)&mtv};
@@ -986,12 +974,5 @@ extern "C" int mvs_launch_moments(const SceneDev* sc, const MomentsDev* mt, hipS
 extern "C" int mvs_launch_score_tab(const SceneDev* sc, const ScoreArgs* a, const TiledArgs* t, const MomentsDev* mt,
                                     hipStream_t s) {
     if (sc->V > 64 || t->chunk != kTabChunk) return -3;
-    switch (mt->wid) {
-        case 1: return launch_tab_w<1>(sc, a, t, mt, s);
-        case 2: return launch_tab_w<2>(sc, a, t, mt, s);
-        case 3: return launch_tab_w<3>(sc, a, t, mt, s);
-        case 4: return launch_tab_w<4>(sc, a, t, mt, s);
-        case 5: return launch_tab_w<5>(sc, a, t, mt, s);
-        default: return -2;
-    }
+    return dispatch_wid(mt->wid, -2, [&](auto w) { return launch_tab_w<decltype(w)::value>(sc, a, t, mt, s); });
 }

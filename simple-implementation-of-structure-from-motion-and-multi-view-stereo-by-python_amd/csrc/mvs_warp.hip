@@ -29,29 +29,6 @@ struct WarpSample {
     double a;         // reference gray value - 128
 };
 
-DEV double wave_sum_f64(double x) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-DEV int wave_sum_i32(int x) {
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
-
-// 1 / w from v_rcp_f64 and two Newton steps: within about an ulp, NOT the
-// correctly rounded quotient that project() gets from an IEEE division (a
-// dozen instructions more, twice per sample).  That is enough here: the
-// positions it feeds are samples of this test alone, not the xy output (which
-// stays project()'s, bit for bit), and an ulp of 1/z moves a sample by
-// ~1e-13 px against the 1.5e-12 px between binary64 formulations of the same
-// position that the tests' tolerance is built on.
-DEV double recip(double w) {
-    double r = __builtin_amdgcn_rcp(w);
-    r = fma(fma(-w, r, 1.0), r, r);
-    r = fma(fma(-w, r, 1.0), r, r);
-    return r;
-}
-
 template <int WID>
 __global__ __launch_bounds__(256) void k_score_warp(const SceneDev sc, const WarpArgs a) {
     constexpr int S = 2 * WID + 1, N = S * S;
@@ -111,8 +88,8 @@ __global__ __launch_bounds__(256) void k_score_warp(const SceneDev sc, const War
             sa += g;
             saa += g * g;
         }
-        sa = wave_sum_i32(sa);
-        saa = wave_sum_i32(saa);
+        sa = wave_sum(sa);
+        saa = wave_sum(saa);
         Sa = (double)sa;
         Da = (double)(N * saa - sa * sa);   // exact: |.| < 2^31 at N <= 121, |g| <= 128
         valid = Da > 0.0;
@@ -127,10 +104,7 @@ __global__ __launch_bounds__(256) void k_score_warp(const SceneDev sc, const War
             for (int v = lane; v < V; v += 64) ncc_out[v] = nan;
         return;
     }
-    // the wave's own LDS rows: writes above, reads below, in program order
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_publish();
 
     const double Wm1 = (double)(sc.W - 1), Hm1 = (double)(sc.H - 1);
     const double scale = (double)N / (double)(N - 1);
@@ -191,7 +165,7 @@ __global__ __launch_bounds__(256) void k_score_warp(const SceneDev sc, const War
         const uint64_t m = __ballot(pass);
         if (lane == 0) mask[g0 >> 6] = m;
         count += __popcll(m);
-        sum += wave_sum_f64(pass ? ncc : 0.0);
+        sum += wave_sum(pass ? ncc : 0.0);
         if (ncc_out && v < V) ncc_out[v] = ncc;
     }
     if (lane == 0) {
@@ -205,13 +179,8 @@ __global__ __launch_bounds__(256) void k_score_warp(const SceneDev sc, const War
 extern "C" int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStream_t s) {
     if (a->n <= 0) return 0;
     const dim3 grid((unsigned)((a->n + 3) / 4)), block(256);
-    switch (wid) {
-        case 1: hipLaunchKernelGGL(k_score_warp<1>, grid, block, 0, s, *sc, *a); break;
-        case 2: hipLaunchKernelGGL(k_score_warp<2>, grid, block, 0, s, *sc, *a); break;
-        case 3: hipLaunchKernelGGL(k_score_warp<3>, grid, block, 0, s, *sc, *a); break;
-        case 4: hipLaunchKernelGGL(k_score_warp<4>, grid, block, 0, s, *sc, *a); break;
-        case 5: hipLaunchKernelGGL(k_score_warp<5>, grid, block, 0, s, *sc, *a); break;
-        default: return -1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return dispatch_wid(wid, -1, [&](auto w) {
+        hipLaunchKernelGGL(k_score_warp<decltype(w)::value>, grid, block, 0, s, *sc, *a);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    });
 }

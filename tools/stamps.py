@@ -33,13 +33,25 @@ print("scene ready", flush=True)
 ctx = pkg.MvsContext(rgb, K, R, t)
 print("context ready", flush=True)
 lib = pkg._lib.load()
-lib.mvs_read_stamps.argtypes = [ctypes.c_void_p]
-buf = np.zeros(4096 * 16, np.uint64)
+
+
+def read_stamps():
+    """Every stamping unit owns its array (rows 0..2047: the scorer of the
+    scene's shape, k_score_mma or k_score_mma_v; rows 2048+: k_bin): their sum."""
+    tot = np.zeros(4096 * 16, np.uint64)
+    for name in ("mvs_read_stamps_bin", "mvs_read_stamps_mma", "mvs_read_stamps_mma_v"):
+        part = np.zeros(4096 * 16, np.uint64)
+        reader = getattr(lib, name)
+        reader.argtypes = [ctypes.c_void_p]
+        reader(part.ctypes.data)
+        tot += part
+    return tot
+
+
 ctx.score(c, ref, 0.7, wid)
-lib.mvs_read_stamps(buf.ctypes.data)
-before = buf.copy()
+before = read_stamps()
 ctx.score(c, ref, 0.7, wid)
-lib.mvs_read_stamps(buf.ctypes.data)
+buf = read_stamps()
 d = (buf - before).reshape(4096, 16)[:2048].astype(np.float64)   # rows 2048+: k_bin
 items = d[:, 0]
 act = items > 0

@@ -74,13 +74,13 @@ if ok.any():
     for k in sorted(set(items_wg.astype(int))):
         sel = items_wg == k
         print(f"    {int(sel.sum())} workgroups with {k} items: end median {q(e_us[sel], 50):.1f} us")
-# k_bin's phases (rows 2048+ of the mvs_kernels stamps)
-lib.mvs_read_stamps.argtypes = [ctypes.c_void_p]
+# k_bin's phases (rows 2048+ of mvs_bin.hip's stamps)
+lib.mvs_read_stamps_bin.argtypes = [ctypes.c_void_p]
 kbuf = np.zeros(4096 * 16, np.uint64)
-lib.mvs_read_stamps(kbuf.ctypes.data)
+lib.mvs_read_stamps_bin(kbuf.ctypes.data)
 k0 = kbuf.copy()
 ctx.score(c, ref, 0.7, wid)
-lib.mvs_read_stamps(kbuf.ctypes.data)
+lib.mvs_read_stamps_bin(kbuf.ctypes.data)
 kb = (kbuf - k0).reshape(4096, 16)[2048:].astype(np.float64)
 kact = kb[:, 0] > 0
 if kact.any():

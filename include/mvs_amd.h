@@ -199,6 +199,77 @@ int mvs_refine_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const d
                              int wid, double min_cos, int kd, int ka, double astep, double step_scale,
                              double* d_c_out, double* d_nrm_out, int32_t* d_best, double* d_score_best,
                              double* d_scores, void* stream);
+/* ---- Level-synchronous patch expansion driven by the plane-warped test ----
+ * (no reference counterpart: patch_expansion, MVS2.py:308-404, ignores the
+ * normal, cuts every view's window at the reference view's pixel and never
+ * refines).  Three stream-ordered device primitives that a caller runs between
+ * mvs_score_warped_device and mvs_refine_warped_device calls; the chain is
+ * MvsContext.expand_warped.  Cameras (Rp, t, fx fy cx cy, O_v = -Rp_v^T t_v) are
+ * mvs_score_warped's; "projection" is mvs_score's, (x, y, depth).
+ * Cell grid of cell_size s in 1..16: nci = W / s, ncj = H / s (integer
+ * division; pixels past the last full cell belong to no cell); the cell of a
+ * pixel position (x, y) is (int(x) / s, int(y) / s); the centre of cell (i, j)
+ * is the pixel position (i s + (s-1)/2, j s + (s-1)/2).  Occupancy is
+ * occ[v][j][i], uint8, caller-owned, V ncj nci bytes, nonzero = taken.
+ * A job is four int32 (p, v, i, j); job arrays are 16-B aligned.
+ *
+ * mvs_wexp_children_device: child jobs and geometry of n frontier patches
+ * (centre c[3p..], normal nrm[3p..], reference view ref[p], mask[p*words..]).
+ * Per patch p:
+ *   1. the views {ref_p} U {v : mask bit v} (those in 0..V-1) in ascending order;
+ *   2. (x, y, depth) = projection of c_p into v; v is skipped unless depth > 0,
+ *      0 <= x < W, 0 <= y < H (which leaves out nan and inf) and the cell (i, j)
+ *      of (x, y) lies inside the grid;
+ *   3. the neighbours k = 0..3: (i+1, j), (i-1, j), (i, j+1), (i, j-1); one
+ *      outside the grid or with occ[v][j'][i'] != 0 is skipped;
+ *   4. q = that cell's centre, d = Rp_v^T ((q.x-cx_v)/fx_v, (q.y-cy_v)/fy_v, 1),
+ *      den = nrm_p.d, s = nrm_p.(c_p - O_v) / den; skipped unless den != 0 and s
+ *      is finite and > 0;
+ *   5. X = O_v + s d; skipped unless |X - c_p| <= max_dist (> 0, world units);
+ *   6. the child: centre X, the parent's normal bit for bit, reference view v,
+ *      job (p, v, i', j').
+ * d_total[0] = the number of jobs found (it may exceed cap >= 0).  The jobs are
+ * compacted in exactly that sequential order (p, then view, then k) into
+ * d_job (cap*4), d_cc, d_cn (cap*3) and d_cref (cap); only the first cap are
+ * written (cap = 0 counts only: the four arrays may then be NULL).  Two parents may name the same (v, cell): both are kept, the claim
+ * decides.  Products and sums are taken left to right in binary64, unfused; the
+ * order across patches comes from a count pass, a scan and an emit pass
+ * (k_wexp_children, k_wexp_scan), never from atomics: results are deterministic.
+ *
+ * mvs_wexp_claim_device: one winner per (view, cell) among m jobs.  A job
+ * contends when accept != 0 and its score is finite; among the contenders of
+ * one (v, i, j) the highest score wins, compared numerically (-0.0 = +0.0),
+ * ties to the lowest job index.  d_win[k] = 1 for winners, 0 for every other
+ * job.  A job whose (v, i, j) lies outside 0..V-1 x nci x ncj never wins; the
+ * host-pointer variant mvs_wexp_claim (synchronous) returns MVS_E_ARG for it.
+ * The context keeps a per-(view, cell) grid of 12 B per cell, allocated at the
+ * first call and left zero by every call: only the cells that the jobs name
+ * are touched (k_wexp_claim_max / _min / _win / _reset: 64-bit atomic max of an
+ * order-preserving image of the score, then of the complemented index among
+ * its holders).  The result does not depend on scheduling.
+ *
+ * mvs_wexp_mark_device: for every job with d_win != 0, occ[cref][j][i] = 1 at
+ * the job's own cell (no reprojection), and for every view v of the child's
+ * final mask (d_mask, m*words) the cell of the projection of its centre
+ * d_cc[3k..] into v, when depth > 0, 0 <= x < W, 0 <= y < H and the cell lies
+ * inside the grid.  Other bytes stay as they are (k_wexp_mark).
+ *
+ * All three: n (m) = 0 returns MVS_OK, launches nothing and touches no context
+ * state; MVS_E_ARG (message in mvs_last_error) for a scalar out of range, a
+ * NULL pointer, n < 0 or a misaligned job array.  They use none of the scorers'
+ * scratch or counter sets and may be interleaved freely with every other call;
+ * calls on different streams are ordered on their own scratch. */
+int mvs_wexp_children_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm,
+                             const int32_t* d_ref, const uint64_t* d_mask, int cell_size,
+                             const uint8_t* d_occ, double max_dist, int64_t cap, int32_t* d_job,
+                             double* d_cc, double* d_cn, int32_t* d_cref, int64_t* d_total, void* stream);
+int mvs_wexp_claim_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_accept,
+                          const double* d_score, int nci, int ncj, uint8_t* d_win, void* stream);
+int mvs_wexp_claim(mvs_ctx* ctx, int64_t m, const int32_t* job, const uint8_t* accept, const double* score,
+                   int nci, int ncj, uint8_t* win);
+int mvs_wexp_mark_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_win,
+                         const double* d_cc, const int32_t* d_cref, const uint64_t* d_mask, int cell_size,
+                         uint8_t* d_occ, void* stream);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

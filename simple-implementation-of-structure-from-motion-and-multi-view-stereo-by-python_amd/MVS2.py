@@ -124,6 +124,16 @@ def refine_patches_warped(ctx, centroids, normals, ref_views, MIN_NCC=0.7, wid=5
     return ctx.refine_warped(centroids, normals, ref_views, wid=wid, min_ncc=MIN_NCC, min_cos=min_cos, **kw)
 
 
+def expand_patches_warped(ctx, centroids, normals, ref_views, rounds=4, cell_size=2, MIN_NCC=0.7, wid=5,
+                          min_cos=0.3, **kw):
+    """Level-synchronous patch expansion driven by the plane-warped photo test
+    and, with refine_levels > 0, the refinement (no reference counterpart; see
+    MvsContext.expand_warped, which takes the remaining keywords): the dict of
+    patch arrays grown from the seed patches."""
+    return ctx.expand_warped(centroids, normals, ref_views, rounds, cell_size=cell_size, wid=wid, min_ncc=MIN_NCC,
+                             min_cos=min_cos, **kw)
+
+
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):
     """MVS2.py:176-295 on the GPU.  Returns None like the reference; the run's
     counters are left in MVS2.last_stats.

@@ -315,6 +315,17 @@ struct mvs_ctx {
     // nrm_out, score_best], [ref, best, views], scores (its own again)
     DevBuf<double> r_in, r_out, r_scores;
     DevBuf<int32_t> r_int;
+    // the warped expansion's scratch (its own again, ordered by wexp_order):
+    // the children's per-patch counts and offsets, the claim's per-(view,
+    // cell) key and ticket grids (zero between calls) and the host-checked
+    // claim's buffers
+    DevBuf<int32_t> x_cnt;
+    DevBuf<int64_t> x_offs;
+    DevBuf<uint64_t> x_key;
+    DevBuf<uint32_t> x_ticket;
+    DevBuf<int4> x_job;
+    DevBuf<double> x_score;
+    DevBuf<uint8_t> x_flags;
     // tiled scorer scratch
     DevBuf<int32_t> t_tiles, t_cand;
     // mvs_pack_accepted: the pack's row counter and chunk ticket (k_acc_pack
@@ -442,7 +453,7 @@ struct mvs_ctx {
             used = false;
             s = nullptr;
         }
-    } scratch_order, pack_order;
+    } scratch_order, pack_order, wexp_order;
     std::string err;
     void scratch_acquire(hipStream_t s) { scratch_order.acquire(s); }
     void scratch_release(hipStream_t s) { scratch_order.release(s); }
@@ -1476,12 +1487,13 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     // the scratch's last users may be any streams (some perhaps destroyed by now)
-    if (ctx->scratch_order.used || ctx->pack_order.used) (void)hipDeviceSynchronize();
+    if (ctx->scratch_order.used || ctx->pack_order.used || ctx->wexp_order.used) (void)hipDeviceSynchronize();
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->scratch_order.ev) (void)hipEventDestroy(ctx->scratch_order.ev);
     if (ctx->pack_order.ev) (void)hipEventDestroy(ctx->pack_order.ev);
+    if (ctx->wexp_order.ev) (void)hipEventDestroy(ctx->wexp_order.ev);
     delete ctx;
 }
 
@@ -1838,6 +1850,158 @@ int mvs_refine_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nr
     });
 }
 
+// ---- the warped expansion's primitives (mvs_expand_warp.hip) ----
+
+int mvs_wexp_children_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                             const uint64_t* d_mask, int cell_size, const uint8_t* d_occ, double max_dist,
+                             int64_t cap, int32_t* d_job, double* d_cc, double* d_cn, int32_t* d_cref,
+                             int64_t* d_total, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (n < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: n < 0"});
+    if (n > ((int64_t)1 << 31)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: n above 2^31"});
+    if (cell_size < 1 || cell_size > 16)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: cell_size must be in 1..16"});
+    if (!(max_dist > 0.0)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: max_dist must be > 0"});
+    if (cap < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: cap < 0"});
+    if (n == 0) return MVS_OK;
+    if (!d_c || !d_nrm || !d_ref || !d_mask || !d_occ || !d_total ||
+        (cap > 0 && (!d_job || !d_cc || !d_cn || !d_cref)))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: null pointer (the outputs may be NULL when cap is 0)"});
+    if ((uintptr_t)d_job % 16) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: d_job must be 16-B aligned"});
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        ctx->wexp_order.acquire(s);
+        ctx->x_cnt.ensure(n);
+        ctx->x_offs.ensure(n + 1);
+        WexpArgs a{};
+        a.n = n;
+        a.c = d_c;
+        a.nrm = d_nrm;
+        a.ref = d_ref;
+        a.mask = d_mask;
+        a.cell_size = cell_size;
+        a.occ = d_occ;
+        a.max_dist = max_dist;
+        a.cap = cap;
+        a.cnt = ctx->x_cnt.p;
+        a.offs = ctx->x_offs.p;
+        a.job = (int4*)d_job;
+        a.cc = d_cc;
+        a.cn = d_cn;
+        a.cref = d_cref;
+        a.total = d_total;
+        if (mvs_launch_wexp_children(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wexp_children launch failed"};
+        ctx->wexp_order.release(s);
+        return 0;
+    });
+}
+
+static int claim_check(mvs_ctx* ctx, int64_t m, bool ptrs_ok, int nci, int ncj) {
+    if (m < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: m < 0"});
+    if (m > ((int64_t)1 << 31)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: m above 2^31"});
+    if (nci < 1 || ncj < 1 || nci > 65536 || ncj > 65536)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: nci and ncj must be in 1..65536"});
+    if (m > 0 && !ptrs_ok) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: null pointer"});
+    return 0;
+}
+
+// the claim on device pointers; the caller holds wexp_order
+static void claim_launch(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_accept,
+                         const double* d_score, int nci, int ncj, uint8_t* d_win, hipStream_t s) {
+    const size_t cells = (size_t)ctx->V * nci * ncj;
+    if (cells > ctx->x_key.n || cells > ctx->x_ticket.n) {
+        // new grids start clean; every call leaves them clean (hipFree of the old ones waits for their users)
+        ctx->x_key.alloc(cells);
+        ctx->x_ticket.alloc(cells);
+        HIPCHK(hipMemsetAsync(ctx->x_key.p, 0, ctx->x_key.n * sizeof(uint64_t), s));
+        HIPCHK(hipMemsetAsync(ctx->x_ticket.p, 0, ctx->x_ticket.n * sizeof(uint32_t), s));
+    }
+    ClaimArgs a{};
+    a.m = m;
+    a.job = (const int4*)d_job;
+    a.accept = d_accept;
+    a.score = d_score;
+    a.V = ctx->V;
+    a.nci = nci;
+    a.ncj = ncj;
+    a.key = ctx->x_key.p;
+    a.ticket = ctx->x_ticket.p;
+    a.win = d_win;
+    if (mvs_launch_wexp_claim(&a, s) != 0) throw Fail{MVS_E_HIP, "wexp_claim launch failed"};
+}
+
+int mvs_wexp_claim_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_accept,
+                          const double* d_score, int nci, int ncj, uint8_t* d_win, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = claim_check(ctx, m, d_job && d_accept && d_score && d_win, nci, ncj)) return rc;
+    if (m == 0) return MVS_OK;
+    if ((uintptr_t)d_job % 16) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: d_job must be 16-B aligned"});
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        ctx->wexp_order.acquire(s);
+        claim_launch(ctx, m, d_job, d_accept, d_score, nci, ncj, d_win, s);
+        ctx->wexp_order.release(s);
+        return 0;
+    });
+}
+
+int mvs_wexp_claim(mvs_ctx* ctx, int64_t m, const int32_t* job, const uint8_t* accept, const double* score, int nci,
+                   int ncj, uint8_t* win) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = claim_check(ctx, m, job && accept && score && win, nci, ncj)) return rc;
+    if (m == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        for (int64_t k = 0; k < m; ++k) {
+            const int32_t* j = job + 4 * k;
+            if (j[1] < 0 || j[1] >= ctx->V || j[2] < 0 || j[2] >= nci || j[3] < 0 || j[3] >= ncj)
+                throw Fail{MVS_E_ARG, "mvs_wexp_claim: job (view, cell) outside the grid"};
+        }
+        hipStream_t s = ctx->stream;
+        ctx->wexp_order.acquire(s);
+        ctx->x_job.ensure(m);
+        ctx->x_score.ensure(m);
+        ctx->x_flags.ensure(2 * m);
+        uint8_t* d_accept = ctx->x_flags.p;
+        uint8_t* d_win = ctx->x_flags.p + m;
+        HIPCHK(hipMemcpyAsync(ctx->x_job.p, job, m * sizeof(int4), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_accept, accept, m, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->x_score.p, score, m * sizeof(double), hipMemcpyHostToDevice, s));
+        claim_launch(ctx, m, (const int32_t*)ctx->x_job.p, d_accept, ctx->x_score.p, nci, ncj, d_win, s);
+        HIPCHK(hipMemcpyAsync(win, d_win, m, hipMemcpyDeviceToHost, s));
+        ctx->wexp_order.release(s);
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+int mvs_wexp_mark_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_win, const double* d_cc,
+                         const int32_t* d_cref, const uint64_t* d_mask, int cell_size, uint8_t* d_occ,
+                         void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (m < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: m < 0"});
+    if (m > ((int64_t)1 << 31)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: m above 2^31"});
+    if (cell_size < 1 || cell_size > 16)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: cell_size must be in 1..16"});
+    if (m == 0) return MVS_OK;
+    if (!d_job || !d_win || !d_cc || !d_cref || !d_mask || !d_occ)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: null pointer"});
+    if ((uintptr_t)d_job % 16) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: d_job must be 16-B aligned"});
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        MarkArgs a{};
+        a.m = m;
+        a.job = (const int4*)d_job;
+        a.win = d_win;
+        a.cc = d_cc;
+        a.cref = d_cref;
+        a.mask = d_mask;
+        a.cell_size = cell_size;
+        a.occ = d_occ;
+        if (mvs_launch_wexp_mark(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wexp_mark launch failed"};
+        return 0;
+    });
+}
+
 int64_t mvs_exact_hits(mvs_ctx* ctx) {
     if (!ctx) return MVS_E_ARG;
     int32_t h = 0;
@@ -1855,6 +2019,7 @@ int mvs_stream_retiring(mvs_ctx* ctx, void* stream) {
     return guarded(ctx, [&]() {
         ctx->scratch_order.retire((hipStream_t)stream);
         ctx->pack_order.retire((hipStream_t)stream);
+        ctx->wexp_order.retire((hipStream_t)stream);
         return 0;
     });
 }

@@ -92,6 +92,50 @@ struct RefineArgs {
     double* scores;        // n*H (may be null), H = (2 kd + 1)(2 ka + 1)^2
 };
 
+// The warped expansion's three primitives (mvs_expand_warp.hip; device pointers).
+// Children of n frontier patches: cnt (n) and offs (n + 1) are the context's
+// scratch between the count pass, the scan and the emit pass.
+struct WexpArgs {
+    int64_t n;
+    const double* c;        // n*3
+    const double* nrm;      // n*3
+    const int32_t* ref;     // n
+    const uint64_t* mask;   // n*words
+    int cell_size;
+    const uint8_t* occ;     // V*ncj*nci
+    double max_dist;
+    int64_t cap;
+    int32_t* cnt;
+    int64_t* offs;
+    int4* job;              // cap: (parent, view, cell i, cell j)
+    double* cc;             // cap*3
+    double* cn;             // cap*3
+    int32_t* cref;          // cap
+    int64_t* total;         // 1
+};
+// One winner per (view, cell) among m jobs: key (64-bit) and ticket (32-bit)
+// are the context's per-cell grids, V*ncj*nci each, zero between calls.
+struct ClaimArgs {
+    int64_t m;
+    const int4* job;
+    const uint8_t* accept;
+    const double* score;
+    int V, nci, ncj;
+    uint64_t* key;
+    uint32_t* ticket;
+    uint8_t* win;
+};
+struct MarkArgs {
+    int64_t m;
+    const int4* job;
+    const uint8_t* win;
+    const double* cc;       // m*3
+    const int32_t* cref;    // m
+    const uint64_t* mask;   // m*words
+    int cell_size;
+    uint8_t* occ;
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -275,6 +319,12 @@ int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStr
 // one level of the refinement against that test (k_refine_warp,
 // mvs_refine.hip): one wave per candidate, lane = (hypothesis, list view)
 int mvs_launch_refine_warp(const SceneDev* sc, const RefineArgs* a, int wid, hipStream_t s);
+// the warped expansion (mvs_expand_warp.hip): children = k_wexp_children count
+// pass, k_wexp_scan, emit pass; claim = k_wexp_claim_max / _min / _win / _reset;
+// mark = k_wexp_mark
+int mvs_launch_wexp_children(const SceneDev* sc, const WexpArgs* a, hipStream_t s);
+int mvs_launch_wexp_claim(const ClaimArgs* a, hipStream_t s);
+int mvs_launch_wexp_mark(const SceneDev* sc, const MarkArgs* a, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

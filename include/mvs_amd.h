@@ -199,6 +199,48 @@ int mvs_refine_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const d
                              int wid, double min_cos, int kd, int ka, double astep, double step_scale,
                              double* d_c_out, double* d_nrm_out, int32_t* d_best, double* d_score_best,
                              double* d_scores, void* stream);
+/* What mvs_refine_warped is fed, built from mvs_score_warped's per-view ncc
+ * (no reference counterpart): per output row k a view list and a depth step.
+ * The source row is s = sel ? sel[k] : k, a row of ncc (rows x V), c (rows x 3)
+ * and ref (rows); views is n x max_views, dstep is n.
+ *   View list, from ncc[s*V .. s*V+V-1]:
+ *   1. view v passes when ncc_v > min_ncc (a binary64 comparison: nan never
+ *      passes, +inf does);
+ *   2. a passing view v is selected when fewer than max_views passing views u
+ *      have ncc_u > ncc_v, or ncc_u == ncc_v with u < v (numeric comparison:
+ *      -0.0 equals +0.0) -- the max_views best, ties to the lower view;
+ *   3. the selected views go to views[k*max_views ..] in ascending view order,
+ *      the remaining slots are -1.
+ *   The list does not depend on ref (the scorer leaves ncc of r at nan).
+ *   Depth step, with r = ref[s], c = c[3s..]: depth = Rp_r[2][0] c.x +
+ *   Rp_r[2][1] c.y + Rp_r[2][2] c.z + t_r[2] (products and sums left to right,
+ *   unfused), dstep[k] = (depth_px depth) / ((fx_r + fy_r) / 2): the world size
+ *   of depth_px pixels at the patch (not clamped: <= 0 or nan for a centre on or
+ *   behind the camera plane or a nan centre, which mvs_refine_warped rejects).
+ * MvsContext.refine_view_lists and refine_depth_steps restate both in numpy;
+ * the results are equal bit for bit.
+ * sel may be NULL (then n <= rows).  dstep may be NULL: lists only, c and ref
+ * are then not read and may be NULL.  max_views in 1..32, min_ncc not nan,
+ * depth_px finite and > 0.  n = 0 returns MVS_OK and launches nothing.
+ * MVS_E_ARG (message in mvs_last_error) for a scalar out of range, n < 0,
+ * rows < 0, n > rows without sel, a NULL required pointer and (host call) a
+ * sel entry outside 0..rows-1 or a ref outside 0..V-1.
+ * Device pointers, stream-ordered (NULL = the context's stream).  A sel entry
+ * outside 0..rows-1 gives an all -1 list and dstep nan and reads nothing of
+ * that row; a ref outside 0..V-1 gives dstep nan.
+ * One kernel (k_refine_lists: one wave per row, lane = view) that reads the
+ * camera table and its arguments only: no scratch, no atomics, no counter sets
+ * and no context state.  It may be interleaved freely with every other call and
+ * run on several streams at once. */
+int mvs_refine_lists_device(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* d_sel,
+                            const double* d_ncc, const double* d_c, const int32_t* d_ref,
+                            double min_ncc, int max_views, double depth_px, int32_t* d_views,
+                            double* d_dstep, void* stream);
+/* Same on host pointers; synchronous, on the context's stream and its own
+ * staging buffers. */
+int mvs_refine_lists(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* sel, const double* ncc,
+                     const double* c, const int32_t* ref, double min_ncc, int max_views,
+                     double depth_px, int32_t* views, double* dstep);
 /* ---- Level-synchronous patch expansion driven by the plane-warped test ----
  * (no reference counterpart: patch_expansion, MVS2.py:308-404, ignores the
  * normal, cuts every view's window at the reference view's pixel and never

@@ -48,6 +48,10 @@ SIGNATURES = [
     ("mvs_refine_warped_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
                                                 ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                 ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mvs_refine_lists_device", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, _vp,
+                                               ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp]),
+    ("mvs_refine_lists", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _i64p, _dp, _dp, _i32p,
+                                        ctypes.c_double, ctypes.c_int, ctypes.c_double, _i32p, _dp]),
     ("mvs_wexp_children_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
                                                 ctypes.c_double, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mvs_wexp_claim_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int,
@@ -544,18 +548,84 @@ class MvsContext:
         depth = Rp[ref, 2, 0] * c[:, 0] + Rp[ref, 2, 1] * c[:, 1] + Rp[ref, 2, 2] * c[:, 2] + t[ref, 2]
         return depth_px * depth / ((K[ref, 0, 0] + K[ref, 1, 1]) / 2)
 
+    def refine_lists_device(self, ncc, c, ref, views, dstep, sel=None, min_ncc=0.7, max_views=8, depth_px=1.5,
+                            stream=None):
+        """refine_view_lists and refine_depth_steps on the device
+        (mvs_refine_lists_device), bit for bit, on torch device tensors
+        (contiguous): ncc float64 (rows,V) as score_warped_device writes it, c
+        float64 (rows,3), ref int32 (rows,), views int32 (n,max_views) and dstep
+        float64 (n,) the outputs, sel int64 (n,) or None -- output row k is made
+        from source row sel[k] (None: row k, n <= rows).  dstep None: lists
+        only, c and ref may then be None.  A sel entry outside 0..rows-1 gives
+        an all -1 list and dstep nan; a ref outside 0..V-1 gives dstep nan.
+        Stream-ordered (stream = a hipStream_t handle, None = the context's);
+        the call keeps no state and may run on several streams at once."""
+        rows = int(ncc.shape[0]) if ncc.dim() == 2 else 0
+        n = int(views.shape[0]) if views.dim() == 2 else 0
+        want = [("ncc", ncc, 8, (rows, self.V)), ("views", views, 4, (n, int(max_views)))]
+        if dstep is not None:
+            if c is None or ref is None:
+                raise RuntimeError("refine_lists_device: dstep needs c and ref")
+            want += [("c", c, 8, (rows, 3)), ("ref", ref, 4, (rows,)), ("dstep", dstep, 8, (n,))]
+        if sel is not None:
+            want.append(("sel", sel, 8, (n,)))
+        for name, x, size, shape in want:
+            # the kernel indexes rows at a fixed pitch
+            if x.dtype.itemsize != size or x.dtype.is_floating_point != (name in ("ncc", "c", "dstep")) or \
+                    tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"refine_lists_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        rc = load().mvs_refine_lists_device(self._h, n, rows, ptr(sel), ncc.data_ptr(),
+                                            ptr(c) if dstep is not None else None,
+                                            ptr(ref) if dstep is not None else None, float(min_ncc), int(max_views),
+                                            float(depth_px), views.data_ptr(), ptr(dstep),
+                                            stream if stream is not None else None)
+        check(rc, self._h, "mvs_refine_lists_device")
+
+    def refine_lists(self, ncc, c=None, ref=None, sel=None, min_ncc=0.7, max_views=8, depth_px=1.5):
+        """refine_lists_device on host arrays (mvs_refine_lists, synchronous):
+        ncc (rows,V), c (rows,3) and ref (rows,) or both None (lists only), sel
+        (n,) int64 or None.  A sel entry outside 0..rows-1 or a ref outside
+        0..V-1 raises.  Returns views (n,max_views) int32 and dstep (n,) float64
+        (None without c and ref)."""
+        ncc = _c(ncc, np.float64)
+        if ncc.ndim != 2 or ncc.shape[1] != self.V:
+            raise RuntimeError(f"refine_lists: ncc must be (rows, {self.V})")
+        rows = len(ncc)
+        if (c is None) != (ref is None):
+            raise RuntimeError("refine_lists: c and ref go together")
+        if c is not None:
+            c = _c(c, np.float64).reshape(-1, 3)
+            ref = _c(ref, np.int32).reshape(-1)
+            if len(c) != rows or len(ref) != rows:
+                raise RuntimeError("refine_lists: ncc, c and ref lengths differ")
+        if sel is not None:
+            sel = _c(sel, np.int64).reshape(-1)
+        n = len(sel) if sel is not None else rows
+        mv = int(max_views)
+        views = np.empty((n, mv if 1 <= mv <= 32 else 1), np.int32)
+        dstep = np.empty(n) if c is not None else None
+        rc = load().mvs_refine_lists(self._h, n, rows, _p(sel, _i64p) if sel is not None else None, _p(ncc, _dp),
+                                     _p(c, _dp) if c is not None else None,
+                                     _p(ref, _i32p) if c is not None else None, float(min_ncc), mv, float(depth_px),
+                                     _p(views, _i32p), _p(dstep, _dp) if dstep is not None else None)
+        check(rc, self._h, "mvs_refine_lists")
+        return views, dstep
+
     def refine_warped(self, c, nrm, ref, wid=5, min_ncc=0.7, min_cos=0.0, max_views=8, levels=4, kd=2, ka=1,
                       depth_px=1.5, astep=math.radians(8)):
         """Coarse-to-fine depth and normal refinement of patches against the
-        plane-warped photo test:
-          1. score_warped with per-view ncc;
-          2. per patch the view list of refine_view_lists (the max_views best
-             passing views);
-          3. dstep = the world size of depth_px pixels at the patch;
+        plane-warped photo test, one upload, one chain on the context's side
+        stream, one download:
+          1. score_warped_device with per-view ncc;
+          2. refine_lists_device: per patch the view list of refine_view_lists
+             (the max_views best passing views) and
+          3. dstep = the world size of depth_px pixels at the patch
+             (refine_depth_steps);
           4. `levels` level calls (refine_warped_level_device) with step_scale
              = 2^-level, c / nrm ping-ponging between two device buffers, no
              host synchronisation in between;
-          5. score_warped of the refined patches.
+          5. score_warped_device of the refined patches.
         A patch with no passing view, or invalid in its reference view, comes
         back unchanged (best -1 at every level).
 
@@ -573,23 +643,31 @@ class MvsContext:
             raise RuntimeError("refine_warped: levels must be >= 1")
         if not 1 <= int(max_views) <= 32:
             raise RuntimeError("refine_warped: max_views must be in 1..32")
+        if len(c) != n or len(nrm) != n:
+            raise RuntimeError("c, nrm and ref lengths differ")
+        if n and (ref.min() < 0 or ref.max() >= self.V):
+            raise RuntimeError("refine_warped: ref view out of range")
         H = self.refine_hypotheses(kd, ka)
-        ncc = self.score_warped(c, nrm, ref, min_ncc, wid, min_cos, want_ncc=True)[4]
-        views = self.refine_view_lists(ncc, min_ncc, int(max_views))
-        dstep = self.refine_depth_steps(c, ref, depth_px)
         dev = torch.device(f"cuda:{self.device}")
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        # a torch side stream of this context carries the whole chain (the
-        # handle of torch's default stream is 0, which the C-ABI reads as "the
-        # context's own stream")
-        if self._refine_stream is None:
-            self._refine_stream = torch.cuda.Stream(dev)
-        st = self._refine_stream
+        # the context's torch side stream carries the whole chain
+        st = self._side_stream()
         with torch.cuda.stream(st):
             cur = [torch.from_numpy(c).to(dev), torch.from_numpy(nrm).to(dev)]
             nxt = [torch.empty((n, 3), **f64), torch.empty((n, 3), **f64)]
-            t_ref, t_views, t_dstep = (torch.from_numpy(x).to(dev) for x in (ref, views, dstep))
+            t_ref = torch.from_numpy(ref).to(dev)
+            xy = torch.empty((n, 2), **f64)
+            mask = torch.empty((n, self.words), dtype=torch.int64, device=dev)
+            count = torch.empty(n, **i32)
+            avg = torch.empty(n, **f64)
+            ncc = torch.empty((n, self.V), **f64)
+            self.score_warped_device(cur[0], cur[1], t_ref, xy, mask, count, None, ncc, min_ncc, wid, min_cos,
+                                     stream=st.cuda_stream)
+            t_views = torch.empty((n, int(max_views)), **i32)
+            t_dstep = torch.empty(n, **f64)
+            self.refine_lists_device(ncc, cur[0], t_ref, t_views, t_dstep, None, min_ncc, int(max_views), depth_px,
+                                     stream=st.cuda_stream)
             best = torch.empty((levels, n), **i32)
             sbest = torch.empty(n, **f64)
             first = torch.empty((n, H), **f64)
@@ -598,13 +676,9 @@ class MvsContext:
                                                 sbest, first if lev == 0 else None, wid, min_cos, kd, ka, astep,
                                                 2.0 ** -lev, stream=st.cuda_stream)
                 cur, nxt = nxt, cur
-            xy = torch.empty((n, 2), **f64)
-            mask = torch.empty((n, self.words), dtype=torch.int64, device=dev)
-            count = torch.empty(n, **i32)
-            avg = torch.empty(n, **f64)
             self.score_warped_device(cur[0], cur[1], t_ref, xy, mask, count, avg, None, min_ncc, wid, min_cos,
                                      stream=st.cuda_stream)
-            info = {"views": views, "best": best.cpu().numpy(),
+            info = {"views": t_views.cpu().numpy(), "best": best.cpu().numpy(),
                     "score_first": first[:, (H - 1) // 2].cpu().numpy(), "score_last": sbest.cpu().numpy()}
             out = (cur[0].cpu().numpy(), cur[1].cpu().numpy(),
                    (xy.cpu().numpy(), mask.cpu().numpy().view(np.uint64), count.cpu().numpy(), avg.cpu().numpy()),
@@ -784,8 +858,9 @@ class MvsContext:
             seed's projection into ref); a seed outside the grid is not accepted;
           every round: score_warped_device of the candidates; accept = count >=
             vlb; one winner per (view, cell) by the highest avg (wexp_claim);
-            with refine_levels > 0 the winners are refined (refine_view_lists,
-            refine_depth_steps(depth_px), refine_levels level calls at step_scale
+            with refine_levels > 0 the winners are refined (refine_lists_device:
+            the rule of refine_view_lists and refine_depth_steps(depth_px) on the
+            device; refine_levels level calls at step_scale
             2^-level, kd 2, ka 1) and re-scored, and the refined patch replaces
             the winner when its count >= vlb and its avg >= the winner's; the
             winners' cells are filled (wexp_mark) with their final masks; the
@@ -797,15 +872,16 @@ class MvsContext:
         max_dist None: 2 cell_size pixels at the first seed's depth in its
         reference view.  Everything runs on one torch side stream; the host
         reads two counters once per round (the next round's job total and this
-        round's winners) and, with refinement, makes the view-list rule's round
-        trip (per-view ncc of the winners to the host, lists back).
+        round's winners) and, with refinement, the winners' number once more
+        (it sizes their buffers); no array crosses to the host inside a round.
 
         Returns a dict of numpy arrays over the patch set: c, nrm (P,3), ref
         (P,), mask (P,words) uint64, count, avg, round, parent (index into the
         patch set, -1 for seeds), cell (P,2) and occ (V,ncj,nci), max_dist.  With
         trace=True also "trace": per round a dict of jobs, cc, cn, cref, xy,
-        mask, count, avg, ncc (as scored), accept, win, kept (winners whose
-        refined patch replaced them), refined (c, nrm, count, avg of the
+        mask, count, avg, ncc (as scored), accept, win, lists (nw, max_views)
+        and dstep (nw,) fed to the level calls, kept (winners whose refined
+        patch replaced them), refined (c, nrm, count, avg of the
         winners' refined patches, in winner order) and occ after marking.
         timer: an optional callable timer(phase, round) called on the chain's
         stream before each phase and with phase "end" after the last."""
@@ -889,14 +965,14 @@ class MvsContext:
                           "count": count.clone(), "avg": avg.clone(), "ncc": ncc, "accept": accept, "win": win}
                 if refine_levels > 0:
                     tick("refine", rnd)
-                    # the list rule's round trip: the winners' ncc to the host, their lists back
-                    idx = torch.nonzero(win).reshape(-1)
+                    # the winners' view lists and depth steps, from the round's ncc on the device
+                    idx = torch.nonzero(win).reshape(-1)   # sizes the winners' buffers: the phase's one read
                     nw = int(idx.numel())
                     if nw:
                         wc, wn, wr_ = cc[idx].contiguous(), cn[idx].contiguous(), cref[idx].contiguous()
-                        lists = self.refine_view_lists(ncc[idx].cpu().numpy(), min_ncc, int(max_views))
-                        dstep = self.refine_depth_steps(wc.cpu().numpy(), wr_.cpu().numpy(), depth_px)
-                        t_lists, t_dstep = torch.from_numpy(lists).to(dev), torch.from_numpy(dstep).to(dev)
+                        t_lists, t_dstep = torch.empty((nw, int(max_views)), **i32), torch.empty(nw, **f64)
+                        self.refine_lists_device(ncc, cc, cref, t_lists, t_dstep, idx, min_ncc, int(max_views),
+                                                 depth_px, stream=sh)
                         cur, nxt = [wc, wn], [torch.empty((nw, 3), **f64), torch.empty((nw, 3), **f64)]
                         best, sbest = torch.empty(nw, **i32), torch.empty(nw, **f64)
                         for lev in range(refine_levels):
@@ -915,6 +991,7 @@ class MvsContext:
                         cc[ki], cn[ki] = cur[0][kept], cur[1][kept]
                         mask[ki], count[ki], avg[ki] = mask2[kept], count2[kept], avg2[kept]
                         if trace:
+                            tr["lists"], tr["dstep"] = t_lists, t_dstep
                             tr["kept"] = kept.to(torch.uint8)
                             tr["refined"] = {"c": cur[0], "nrm": cur[1], "count": count2, "avg": avg2}
                 tick("mark", rnd)

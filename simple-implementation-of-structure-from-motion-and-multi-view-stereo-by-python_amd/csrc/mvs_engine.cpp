@@ -315,6 +315,11 @@ struct mvs_ctx {
     // nrm_out, score_best], [ref, best, views], scores (its own again)
     DevBuf<double> r_in, r_out, r_scores;
     DevBuf<int32_t> r_int;
+    // mvs_refine_lists's host-pointer buffers: [ncc, c, dstep], [ref, views],
+    // sel (its own again; the device call keeps no state at all)
+    DevBuf<double> l_in;
+    DevBuf<int32_t> l_int;
+    DevBuf<int64_t> l_sel;
     // the warped expansion's scratch (its own again, ordered by wexp_order):
     // the children's per-patch counts and offsets, the claim's per-(view,
     // cell) key and ticket grids (zero between calls) and the host-checked
@@ -1845,6 +1850,98 @@ int mvs_refine_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nr
         HIPCHK(hipMemcpyAsync(score_best, d_sb, n * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(best, d_best, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (scores) HIPCHK(hipMemcpyAsync(scores, ctx->r_scores.p, n * H * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// argument checks shared by the two entry points of the list builder
+static int lists_check(mvs_ctx* ctx, int64_t n, int64_t rows, bool has_sel, bool ptrs_ok, double min_ncc,
+                       int max_views, double depth_px) {
+    if (n < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: n < 0"});
+    if (rows < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: rows < 0"});
+    if (n > ((int64_t)1 << 31) || rows > ((int64_t)1 << 31))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: n or rows above 2^31"});
+    if (max_views < 1 || max_views > 32)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: max_views must be in 1..32"});
+    if (std::isnan(min_ncc)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: min_ncc is nan"});
+    if (!std::isfinite(depth_px) || !(depth_px > 0.0))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: depth_px must be finite and > 0"});
+    if (!has_sel && n > rows) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: n > rows without sel"});
+    if (n > 0 && !ptrs_ok)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: null pointer (only sel and dstep, and c and ref "
+                                            "without dstep, may be NULL)"});
+    return 0;
+}
+
+static void lists_launch(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* d_sel, const double* d_ncc,
+                         const double* d_c, const int32_t* d_ref, double min_ncc, int max_views, double depth_px,
+                         int32_t* d_views, double* d_dstep, hipStream_t s) {
+    ListArgs a{};
+    a.n = n;
+    a.rows = rows;
+    a.sel = d_sel;
+    a.ncc = d_ncc;
+    a.c = d_c;
+    a.ref = d_ref;
+    a.min_ncc = min_ncc;
+    a.depth_px = depth_px;
+    a.max_views = max_views;
+    a.views = d_views;
+    a.dstep = d_dstep;
+    if (mvs_launch_refine_lists(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "refine_lists launch failed"};
+}
+
+int mvs_refine_lists_device(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* d_sel, const double* d_ncc,
+                            const double* d_c, const int32_t* d_ref, double min_ncc, int max_views, double depth_px,
+                            int32_t* d_views, double* d_dstep, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = lists_check(ctx, n, rows, d_sel != nullptr, d_ncc && d_views && (!d_dstep || (d_c && d_ref)),
+                             min_ncc, max_views, depth_px))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        lists_launch(ctx, n, rows, d_sel, d_ncc, d_c, d_ref, min_ncc, max_views, depth_px, d_views, d_dstep, s);
+        return 0;
+    });
+}
+
+int mvs_refine_lists(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* sel, const double* ncc, const double* c,
+                     const int32_t* ref, double min_ncc, int max_views, double depth_px, int32_t* views,
+                     double* dstep) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = lists_check(ctx, n, rows, sel != nullptr, ncc && views && (!dstep || (c && ref)), min_ncc,
+                             max_views, depth_px))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        const int V = ctx->V;
+        for (int64_t k = 0; sel && k < n; ++k)
+            if (sel[k] < 0 || sel[k] >= rows) throw Fail{MVS_E_ARG, "mvs_refine_lists: sel row out of range"};
+        for (int64_t k = 0; dstep && k < n; ++k) {
+            const int32_t r = ref[sel ? sel[k] : k];
+            if (r < 0 || r >= V) throw Fail{MVS_E_ARG, "mvs_refine_lists: ref view out of range"};
+        }
+        hipStream_t s = ctx->stream;
+        // buffers of this call alone: [ncc, c, dstep], [ref, views], sel
+        ctx->l_in.ensure(rows * (V + 3) + n); ctx->l_int.ensure(rows + n * max_views);
+        if (sel) ctx->l_sel.ensure(n);
+        double* d_ncc = ctx->l_in.p;
+        double* d_c = d_ncc + rows * V;
+        double* d_dstep = d_c + rows * 3;
+        int32_t* d_ref = ctx->l_int.p;
+        int32_t* d_views = d_ref + rows;
+        HIPCHK(hipMemcpyAsync(d_ncc, ncc, rows * V * sizeof(double), hipMemcpyHostToDevice, s));
+        if (dstep) {
+            HIPCHK(hipMemcpyAsync(d_c, c, rows * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_ref, ref, rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        if (sel) HIPCHK(hipMemcpyAsync(ctx->l_sel.p, sel, n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        lists_launch(ctx, n, rows, sel ? ctx->l_sel.p : nullptr, d_ncc, d_c, d_ref, min_ncc, max_views, depth_px,
+                     d_views, dstep ? d_dstep : nullptr, s);
+        HIPCHK(hipMemcpyAsync(views, d_views, n * max_views * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (dstep) HIPCHK(hipMemcpyAsync(dstep, d_dstep, n * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     });

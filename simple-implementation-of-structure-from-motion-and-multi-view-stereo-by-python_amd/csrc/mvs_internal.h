@@ -92,6 +92,20 @@ struct RefineArgs {
     double* scores;        // n*H (may be null), H = (2 kd + 1)(2 ka + 1)^2
 };
 
+// Inputs/outputs of the refinement's view-list and depth-step builder
+// (k_refine_lists, mvs_refine.hip; device pointers).
+struct ListArgs {
+    int64_t n, rows;       // output rows, source rows
+    const int64_t* sel;    // n source rows (null: row k is source row k)
+    const double* ncc;     // rows*V, as k_score_warp writes it
+    const double* c;       // rows*3 (unread when dstep is null)
+    const int32_t* ref;    // rows   (unread when dstep is null)
+    double min_ncc, depth_px;
+    int max_views;
+    int32_t* views;        // n*max_views, unused slots -1 at the end
+    double* dstep;         // n (may be null: lists only)
+};
+
 // The warped expansion's three primitives (mvs_expand_warp.hip; device pointers).
 // Children of n frontier patches: cnt (n) and offs (n + 1) are the context's
 // scratch between the count pass, the scan and the emit pass.
@@ -319,6 +333,9 @@ int mvs_launch_score_warp(const SceneDev* sc, const WarpArgs* a, int wid, hipStr
 // one level of the refinement against that test (k_refine_warp,
 // mvs_refine.hip): one wave per candidate, lane = (hypothesis, list view)
 int mvs_launch_refine_warp(const SceneDev* sc, const RefineArgs* a, int wid, hipStream_t s);
+// the view lists and depth steps that kernel is fed (k_refine_lists,
+// mvs_refine.hip): one wave per row, lane = view, no scratch
+int mvs_launch_refine_lists(const SceneDev* sc, const ListArgs* a, hipStream_t s);
 // the warped expansion (mvs_expand_warp.hip): children = k_wexp_children count
 // pass, k_wexp_scan, emit pass; claim = k_wexp_claim_max / _min / _win / _reset;
 // mark = k_wexp_mark

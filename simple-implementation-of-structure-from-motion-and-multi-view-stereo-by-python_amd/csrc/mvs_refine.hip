@@ -25,6 +25,21 @@
 // A wave keeps to its own LDS rows: no workgroup barrier, no scratch buffer
 // in memory, no atomics.  Binary64 throughout on s = g - 128; compiled with
 // -ffp-contract=off (fused products are the ones written as fma()).
+//
+// k_refine_lists: what the level kernel is fed, built on the device
+// (mvs_refine_lists, include/mvs_amd.h): per row the view list -- the
+// max_views best passing views of a row of k_score_warp's ncc, ties to the
+// lower view, in ascending view order -- and the depth step.  One wave per
+// row, four rows per workgroup, lane = view: a row's 8 V bytes are one
+// coalesced load, at V > 64 a lane holds one key per group of 64 views (G of
+// them, in registers).  A key's rank is counted in a loop over the passing
+// keys (the set bits of their ballot: a handful per scored row), each
+// broadcast from its lane (v_readlane, the lane index is uniform); the
+// output slot of a selected view is the number of selected lower views (a
+// ballot and mbcnt per group, plus the lower groups' popcounts): ascending
+// order with no sort.  Lane 0 computes the depth step from the camera table.
+// No LDS, no atomics, no scratch: a memory stream of n (8 V + 4 max_views + 44)
+// bytes.
 #include "mvs_device.h"
 
 namespace {
@@ -313,7 +328,98 @@ __global__ __launch_bounds__(256) void k_refine_warp(const SceneDev sc, const Re
     }
 }
 
+// x of lane l (wave-uniform) on every lane
+DEV double lane_bcast(double x, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
+    return __hiloint2double(hi, lo);
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void k_refine_lists(const SceneDev sc, const ListArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+    if (k >= a.n) return;
+    const int V = sc.V, mv = a.max_views;
+    const double nan = __builtin_nan(""), ninf = -__builtin_inf();
+    int64_t s = a.sel ? a.sel[k] : k;   // one address per wave
+    s = ((int64_t)__builtin_amdgcn_readfirstlane((int)(s >> 32)) << 32) |
+        (uint32_t)__builtin_amdgcn_readfirstlane((int)s);
+    int32_t* const out = a.views + k * mv;
+    if (s < 0 || s >= a.rows) {   // nothing of the row is read
+        if (lane < mv) out[lane] = -1;
+        if (lane == 0 && a.dstep) a.dstep[k] = nan;
+        return;
+    }
+    // view v = 64 g + lane holds key[g]: its ncc when it passes, else -inf (a
+    // passing ncc is above min_ncc, so above -inf: -inf never outranks or ties it)
+    double key[G];
+    const double* const row = a.ncc + s * V;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const int v = 64 * g + lane;
+        const double x = v < V ? row[v] : nan;
+        key[g] = x > a.min_ncc ? x : ninf;   // nan never passes, +inf does
+    }
+    // rank[g] = the passing views u that go before v: key_u > key_v, or equal
+    // and u < v.  Only passing views can go before a passing one, so the loop
+    // walks the set bits of their ballot (a scored row passes a handful of
+    // its V views, most rows none)
+    int rank[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) rank[g] = 0;
+#pragma unroll
+    for (int gu = 0; gu < G; ++gu) {
+        for (uint64_t pm = __ballot(key[gu] > ninf); pm; pm &= pm - 1) {
+            const int l = __builtin_ctzll(pm);
+            const double ku = lane_bcast(key[gu], l);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const bool lower = gu < g || (gu == g && l < lane);
+                rank[g] += (ku > key[g] || (ku == key[g] && lower)) ? 1 : 0;
+            }
+        }
+    }
+    int total = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const bool chosen = key[g] > ninf && rank[g] < mv;
+        const uint64_t b = __ballot(chosen);
+        const int slot = total + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        if (chosen) out[slot] = 64 * g + lane;   // slot < mv: at most mv views have a rank below mv
+        total += __popcll(b);
+    }
+    if (lane >= total && lane < mv) out[lane] = -1;
+    if (lane == 0 && a.dstep) {
+        const int r = a.ref[s];
+        double d = nan;
+        if (r >= 0 && r < V) {
+            const CamDev& cr = sc.cams[r];
+            const double* const c = a.c + 3 * s;
+            const double depth = cr.Rp[6] * c[0] + cr.Rp[7] * c[1] + cr.Rp[8] * c[2] + cr.t[2];
+            d = (a.depth_px * depth) / ((cr.fx + cr.fy) / 2);
+        }
+        a.dstep[k] = d;
+    }
+}
+
 }  // namespace
+
+extern "C" int mvs_launch_refine_lists(const SceneDev* sc, const ListArgs* a, hipStream_t s) {
+    if (a->n <= 0) return 0;
+    const dim3 grid((unsigned)((a->n + 3) / 4)), block(256);
+    switch ((sc->V + 63) / 64) {
+        case 1: hipLaunchKernelGGL(k_refine_lists<1>, grid, block, 0, s, *sc, *a); break;
+        case 2: hipLaunchKernelGGL(k_refine_lists<2>, grid, block, 0, s, *sc, *a); break;
+        case 3: hipLaunchKernelGGL(k_refine_lists<3>, grid, block, 0, s, *sc, *a); break;
+        case 4: hipLaunchKernelGGL(k_refine_lists<4>, grid, block, 0, s, *sc, *a); break;
+        default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+static_assert(MVS_MAX_VIEWS == 256, "k_refine_lists holds at most four keys per lane");
 
 extern "C" int mvs_launch_refine_warp(const SceneDev* sc, const RefineArgs* a, int wid, hipStream_t s) {
     if (a->n <= 0) return 0;

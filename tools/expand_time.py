@@ -10,7 +10,7 @@ timed runs (the median run is reported).  Prints one JSON line; per round:
   device milliseconds between the chain's phase marks (events on its stream):
     score     mvs_score_warped_device of the round's jobs
     claim     accept flags (a torch op) + k_wexp_claim_max / _min / _win / _reset
-    refine    the winners' refinement: list round trip, level calls, re-score
+    refine    the winners' refinement: k_refine_lists, level calls, re-score
     mark      k_wexp_mark
     children  the frontier's masking (torch ops) + k_wexp_children count pass,
               k_wexp_scan, emit pass

@@ -15,6 +15,15 @@ and the baseline timed in the same process: the same H n hypotheses expanded
 into H n candidates of score_warped_device with ncc output -- what a caller
 had to do before this call existed -- with the ratio baseline / level.
 
+A third child times the `lists` entry on the same rows: the device builder of
+the view lists and depth steps (mvs_refine_lists_device, kernel k_refine_lists)
+on the scorer's own ncc --
+
+  us_per_call (device events, the same windows), floor_bytes = n (8 V +
+  4 max_views + 44) and floor_us_at_8TBs, and host_path_us: the wall time of
+  what the call replaces (ncc to the host, refine_view_lists,
+  refine_depth_steps, lists and steps back), median of the same number of runs.
+
 A pair is counted for every hypothesis of a patch that passes the candidate
 test (the kernel skips the samples of a pair that fails its facing test, so
 samples_per_s is an upper bound by that share).
@@ -35,6 +44,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "simple-implementation-of-structure-from-motion-and-multi-view-stereo-by-python_amd"
 DATA = os.path.join(REPO, "data", "dinoRing")
 KD, KA, ASTEP, MAX_VIEWS, MIN_NCC = 2, 1, math.radians(8), 8, 0.7
+HBM_BYTES_PER_S = 8e12   # the rate DESIGN's byte floors are taken against
 
 
 def expand(c, nrm, ref, O, dstep):
@@ -140,6 +150,67 @@ def child(a):
                       "baseline_us_max": round(ub[-1], 2), "baseline_over_level": bmed / med}))
 
 
+def child_lists(a):
+    """The `lists` entry: refine_lists_device on the scorer's ncc of the same
+    2^14 rows, against the byte floor and the host path it replaces."""
+    import time
+    import torch
+    assert torch.cuda.is_available(), "refine_time needs the GPU"
+    mvs = importlib.import_module(PKG)
+    sys.path.insert(0, os.path.join(REPO, "tests", "golden"))
+    from make_seeds import load_dino
+    imgs, K, R, t = load_dino(DATA)
+    rgb = np.stack(imgs)
+    c, ref = mvs.synthetic.candidates(a.n, K, R, t, seed=0)
+    dev = torch.device("cuda:0")
+    n, wid = a.n, 5
+    with mvs.MvsContext(rgb, K, R, t, device=0) as ctx:
+        V = ctx.V
+        O = -np.einsum("vji,vj->vi", ctx.rproj(), t.reshape(-1, 3))
+        nrm = O[ref] - c
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        st = torch.cuda.Stream(dev)
+        with torch.cuda.stream(st):
+            tc, tn, tr = (torch.from_numpy(v).to(dev) for v in (c, nrm, ref))
+            xy = torch.empty((n, 2), dtype=torch.float64, device=dev)
+            mask = torch.empty((n, ctx.words), dtype=torch.int64, device=dev)
+            cnt = torch.empty(n, dtype=torch.int32, device=dev)
+            ncc = torch.empty((n, V), dtype=torch.float64, device=dev)
+            ctx.score_warped_device(tc, tn, tr, xy, mask, cnt, None, ncc, MIN_NCC, wid, a.min_cos,
+                                    stream=st.cuda_stream)
+            views = torch.empty((n, MAX_VIEWS), dtype=torch.int32, device=dev)
+            dstep = torch.empty(n, dtype=torch.float64, device=dev)
+
+            def lists():
+                ctx.refine_lists_device(ncc, tc, tr, views, dstep, None, MIN_NCC, MAX_VIEWS, 1.5,
+                                        stream=st.cuda_stream)
+            us = timed(torch, st, lists, a.calls, a.windows)
+            # what the call replaces, wall time: ncc to the host, the numpy rule, lists and steps back
+            host = []
+            for _ in range(a.windows):
+                st.synchronize()
+                t0 = time.perf_counter()
+                h_ncc = ncc.cpu().numpy()
+                hv = ctx.refine_view_lists(h_ncc, MIN_NCC, MAX_VIEWS)
+                hd = ctx.refine_depth_steps(tc.cpu().numpy(), tr.cpu().numpy(), 1.5)
+                t_hv, t_hd = torch.from_numpy(hv).to(dev), torch.from_numpy(hd).to(dev)
+                st.synchronize()
+                host.append((time.perf_counter() - t0) * 1e6)
+            host.sort()
+            same = bool(torch.equal(t_hv, views)) and t_hd.cpu().numpy().tobytes() == dstep.cpu().numpy().tobytes()
+    med = us[len(us) // 2]
+    floor_bytes = n * (8 * V + 4 * MAX_VIEWS + 44)
+    floor_us = floor_bytes / HBM_BYTES_PER_S * 1e6
+    print(json.dumps({"n": n, "V": V, "max_views": MAX_VIEWS, "calls_per_window": a.calls, "windows": a.windows,
+                      "us_per_call": round(med, 2), "us_min": round(us[0], 2), "us_max": round(us[-1], 2),
+                      "floor_bytes": floor_bytes, "floor_us_at_8TBs": round(floor_us, 2),
+                      "time_over_floor": round(med / floor_us, 2),
+                      "rows_with_a_list": int((views >= 0).any(1).sum().item()),
+                      "host_path_us": round(host[len(host) // 2], 1), "host_path_us_min": round(host[0], 1),
+                      "host_path_us_max": round(host[-1], 1), "host_path_over_call": round(host[len(host) // 2] / med, 1),
+                      "equal_to_host_path": same}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 14)
@@ -148,10 +219,11 @@ def main():
     ap.add_argument("--min-cos", type=float, default=0.3)
     ap.add_argument("--limit", type=int, default=300, help="seconds allowed to each wid's process")
     ap.add_argument("--wid", type=int, default=0, help="(child) the one wid to time")
+    ap.add_argument("--lists", action="store_true", help="(child) time refine_lists_device")
     a = ap.parse_args()
-    if a.wid:
+    if a.wid or a.lists:
         sys.path.insert(0, REPO)
-        child(a)
+        child_lists(a) if a.lists else child(a)
         return 0
     out = {"kernel": "k_refine_warp", "scene": "dinoRing 48 x 640 x 480", "min_ncc": MIN_NCC, "min_cos": a.min_cos,
            "kd": KD, "ka": KA, "astep_deg": 8, "depth_px": 1.5, "max_views": MAX_VIEWS}
@@ -165,6 +237,14 @@ def main():
             print(json.dumps({"error": f"wid {wid} exited with {p.returncode}", **out}))
             return 1
         out[f"wid{wid}"] = json.loads(p.stdout.strip().splitlines()[-1])
+    cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--lists", "--n", str(a.n),
+           "--calls", str(a.calls), "--windows", str(a.windows), "--min-cos", str(a.min_cos)]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    if p.returncode != 0:
+        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+        print(json.dumps({"error": f"lists exited with {p.returncode}", **out}))
+        return 1
+    out["lists"] = json.loads(p.stdout.strip().splitlines()[-1])
     print(json.dumps(out))
     return 0
 

@@ -312,6 +312,85 @@ int mvs_wexp_claim(mvs_ctx* ctx, int64_t m, const int32_t* job, const uint8_t* a
 int mvs_wexp_mark_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_win,
                          const double* d_cc, const int32_t* d_cref, const uint64_t* d_mask, int cell_size,
                          uint8_t* d_occ, void* stream);
+/* ---- Visibility-consistency filter for warped patch sets ----
+ * (no reference counterpart: filter_out_outlier below knows neither normals
+ * nor depth order).  The fourth stage of the warped pipeline (test, refine,
+ * expand, filter): it removes the patches that contradict the visibility of the
+ * rest of the set.  Two stream-ordered device calls; the chain is
+ * MvsContext.filter_warped.  Cameras, "projection" and the cell grid of
+ * cell_size s in 1..16 are the expansion's above.
+ *
+ * Inputs: n patches, n < 2^31, with centre c[3p..], normal nrm[3p..], reference
+ * view ref[p], mask[p*words..] and avg[p] (mvs_score_warped's), and the scalars
+ * adj_px >= 0 (finite) and min_views >= 0.
+ *   Views.  T(p) = {ref_p} U {v : mask bit v}, those in 0..V-1, ascending.  A row
+ *   whose ref lies outside 0..V-1 is dead: it takes no part and gets vis 0,
+ *   conf 0 and keep 0 (a chain drops patches by setting ref = -1, without
+ *   compacting its arrays).
+ *   Placement.  For v in T(p), (x, y, depth) = projection of c_p into v.  p is
+ *   placed in v when depth > 0, 0 <= x < W, 0 <= y < H and the cell
+ *   (int(x) / s, int(y) / s) lies inside the grid (mvs_wexp_mark's rule).  Its
+ *   depth there is z_p(v) = Rp_v[6] X + Rp_v[7] Y + Rp_v[8] Z + t_v[2], products
+ *   and sums left to right in binary64, unfused.
+ *   Front grid.  front[v][j][i] (int32) = the placed patch of least z in that
+ *   (view, cell), ties to the lowest index; zfront[v][j][i] (binary64) = its z.
+ *   An empty cell holds -1 and +inf.  V ncj nci elements each.
+ *   Adjacency of p and f in view v: d = c_p - c_f, a = |d.nrm_p| + |d.nrm_f|
+ *   (each dot product left to right, unfused), rho = (adj_px z_p(v)) /
+ *   ((fx_v + fy_v) / 2): adj_px pixel footprints at p's depth, the quantity of
+ *   mvs_refine_lists' depth step.  Adjacent iff a < 2 rho; a nan anywhere makes
+ *   them not adjacent.
+ *   Visibility.  Bit v of vis(p) (n*words uint64) is set iff p is placed in v
+ *   and front = p there or p is adjacent in v to the front patch there.
+ *   Conflicts.  F(p) = the SET of front patches f over p's placed views with
+ *   f != p and f not adjacent to p in that view: a patch named in several views
+ *   counts once, and it belongs to F(p) as soon as one placed view has it in
+ *   front and not adjacent (adjacency depends on the view through z_p(v)).
+ *   Weights.  w(p) = floor(clamp(avg_p, 0, 2) 2^32 + 0.5) as int64, 0 when avg_p
+ *   is not finite (the product with 2^32 is exact).
+ *   conf(p) = sum of w(f) over f in F(p) + sum of w(q) over the q with p in
+ *   F(q), in int64: the evidence of the patches that hide p plus that of the
+ *   patches p hides.  Two patches that hide each other in different views
+ *   (p in F(q) and q in F(p)) are counted in both sums, so each gets the
+ *   other's weight twice.  Integer sums do not depend on the order in which the
+ *   atomic adds arrive.
+ *   Decision.  keep(p) = alive and popcount(vis(p)) >= min_views and
+ *   |T(p)| w(p) >= conf(p): PMVS's visibility count, and the patch's own
+ *   support against its conflicting patches' support.
+ *
+ * mvs_wfilt_front_device writes every element of d_front and d_zfront (the
+ * caller's two grids are its only scratch; n = 0 still fills them with -1 and
+ * +inf): k_wfilt_fill, then k_wfilt_front twice -- a 64-bit atomic min of the
+ * depth's bit pattern (positive doubles order as unsigned integers), then an
+ * unsigned 32-bit atomic min of the index among the holders of the minimum.
+ * mvs_wfilt_test_device reads a front grid as given -- it need not come from the
+ * same rows, and a front patch need not be alive; an entry outside -1..n-1 is
+ * read as -1 and a placed view whose cell holds -1 is neither visible nor a
+ * conflict -- zeroes d_conf and writes d_vis, d_conf and d_keep (uint8) of every
+ * row: k_wfilt_conflict (one wave per patch, lane = view; F(p) is made a set
+ * inside the wave; one 64-bit atomic add of w(p) per member onto conf[f] and
+ * one of the members' weights onto conf[p]), then k_wfilt_decide.  n = 0
+ * returns MVS_OK and launches nothing.
+ * Neither call keeps context state: they may run on any stream beside any other
+ * call, and interleave freely with every other call.  Results are deterministic.
+ * The host-pointer variants mvs_wfilt_front and mvs_wfilt_test are synchronous,
+ * on the context's stream and a buffer of their own; mvs_wfilt_test returns
+ * MVS_E_ARG for a front entry outside -1..n-1.
+ * MVS_E_ARG (message in mvs_last_error) for a scalar out of range (cell_size,
+ * adj_px negative, nan or inf, min_views < 0), a NULL pointer, n < 0 or
+ * n >= 2^31. */
+int mvs_wfilt_front_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref,
+                           const uint64_t* d_mask, int cell_size, int32_t* d_front, double* d_zfront,
+                           void* stream);
+int mvs_wfilt_test_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm,
+                          const int32_t* d_ref, const uint64_t* d_mask, const double* d_avg, int cell_size,
+                          double adj_px, int min_views, const int32_t* d_front, uint64_t* d_vis,
+                          int64_t* d_conf, uint8_t* d_keep, void* stream);
+int mvs_wfilt_front(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, const uint64_t* mask,
+                    int cell_size, int32_t* front, double* zfront);
+int mvs_wfilt_test(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                   const uint64_t* mask, const double* avg, int cell_size, double adj_px, int min_views,
+                   const int32_t* front, uint64_t* vis, int64_t* conf, uint8_t* keep);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

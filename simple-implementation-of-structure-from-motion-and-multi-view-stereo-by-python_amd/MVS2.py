@@ -134,6 +134,14 @@ def expand_patches_warped(ctx, centroids, normals, ref_views, rounds=4, cell_siz
                              min_cos=min_cos, **kw)
 
 
+def filter_patches_warped(ctx, patches, **kw):
+    """Visibility-consistency filter of a warped patch set (no reference
+    counterpart; see MvsContext.filter_warped, which takes the keywords):
+    `patches` is the dict expand_patches_warped returns; the surviving patches
+    with their rows in the input, the front grid and the occupancy."""
+    return ctx.filter_warped(patches, **kw)
+
+
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):
     """MVS2.py:176-295 on the GPU.  Returns None like the reference; the run's
     counters are left in MVS2.last_stats.

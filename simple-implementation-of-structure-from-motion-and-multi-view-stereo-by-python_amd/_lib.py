@@ -59,6 +59,12 @@ SIGNATURES = [
     ("mvs_wexp_claim", ctypes.c_int, [_vp, ctypes.c_int64, _i32p, _u8p, _dp, ctypes.c_int, ctypes.c_int, _u8p]),
     ("mvs_wexp_mark_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
                                             _vp]),
+    ("mvs_wfilt_front_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp]),
+    ("mvs_wfilt_test_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                             ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("mvs_wfilt_front", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _u64p, ctypes.c_int, _i32p, _dp]),
+    ("mvs_wfilt_test", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, _u64p, _dp, ctypes.c_int,
+                                      ctypes.c_double, ctypes.c_int, _i32p, _u64p, _i64p, _u8p]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -1057,6 +1063,163 @@ class MvsContext:
                 res["trace"] = [host(tr) for tr in traces]
         st.synchronize()
         return res
+
+    # ---- visibility-consistency filter of a warped patch set ----
+
+    def wfilt_front_device(self, c, ref, mask, cell_size, front, zfront, stream=None):
+        """mvs_wfilt_front_device on torch device tensors (contiguous: c float64
+        (n,3), ref int32 (n,), mask int64 (n,words), front int32 and zfront
+        float64 (V,ncj,nci), both written whole); stream-ordered."""
+        n = int(ref.numel())
+        nci, ncj = self.cell_grid(cell_size)
+        for name, x, size, shape in [("c", c, 8, (n, 3)), ("ref", ref, 4, (n,)), ("mask", mask, 8, (n, self.words)),
+                                     ("front", front, 4, (self.V, ncj, nci)),
+                                     ("zfront", zfront, 8, (self.V, ncj, nci))]:
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wfilt_front_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wfilt_front_device(self._h, n, c.data_ptr(), ref.data_ptr(), mask.data_ptr(), int(cell_size),
+                                           front.data_ptr(), zfront.data_ptr(), self._stream_handle(stream))
+        check(rc, self._h, "mvs_wfilt_front_device")
+
+    def wfilt_test_device(self, c, nrm, ref, mask, avg, cell_size, adj_px, min_views, front, vis, conf, keep,
+                          stream=None):
+        """mvs_wfilt_test_device on torch device tensors (contiguous: c, nrm
+        float64 (n,3), ref int32 (n,), mask int64 (n,words), avg float64 (n,),
+        front int32 (V,ncj,nci), vis int64 (n,words), conf int64 (n,), keep uint8
+        (n,)); stream-ordered."""
+        n = int(ref.numel())
+        nci, ncj = self.cell_grid(cell_size)
+        for name, x, size, shape in [("c", c, 8, (n, 3)), ("nrm", nrm, 8, (n, 3)), ("ref", ref, 4, (n,)),
+                                     ("mask", mask, 8, (n, self.words)), ("avg", avg, 8, (n,)),
+                                     ("front", front, 4, (self.V, ncj, nci)), ("vis", vis, 8, (n, self.words)),
+                                     ("conf", conf, 8, (n,)), ("keep", keep, 1, (n,))]:
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wfilt_test_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wfilt_test_device(self._h, n, c.data_ptr(), nrm.data_ptr(), ref.data_ptr(), mask.data_ptr(),
+                                          avg.data_ptr(), int(cell_size), float(adj_px), int(min_views),
+                                          front.data_ptr(), vis.data_ptr(), conf.data_ptr(), keep.data_ptr(),
+                                          self._stream_handle(stream))
+        check(rc, self._h, "mvs_wfilt_test_device")
+
+    def wfilt_front(self, c, ref, mask, cell_size):
+        """The front grid of a patch set (mvs_wfilt_front, host pointers): per
+        (view, cell) the placed patch of least depth, ties to the lowest index.
+        Returns front (V,ncj,nci) int32 (-1 = empty) and zfront float64 (+inf)."""
+        nci, ncj = self.cell_grid(cell_size)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        c = _c(c, np.float64).reshape(n, 3)
+        mask = _c(mask, np.uint64).reshape(n, self.words)
+        front = np.empty((self.V, ncj, nci), np.int32)
+        zfront = np.empty((self.V, ncj, nci), np.float64)
+        rc = load().mvs_wfilt_front(self._h, n, _p(c, _dp), _p(ref, _i32p), _p(mask, _u64p), int(cell_size),
+                                    _p(front, _i32p), _p(zfront, _dp))
+        check(rc, self._h, "mvs_wfilt_front")
+        return front, zfront
+
+    def wfilt_test(self, c, nrm, ref, mask, avg, cell_size, adj_px, min_views, front):
+        """The visibility and conflict test of a patch set against a front grid
+        (mvs_wfilt_test, host pointers; a front entry outside -1..n-1 raises).
+        Returns vis (n,words) uint64, conf (n,) int64 and keep (n,) uint8."""
+        nci, ncj = self.cell_grid(cell_size)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        c = _c(c, np.float64).reshape(n, 3)
+        nrm = _c(nrm, np.float64).reshape(n, 3)
+        mask = _c(mask, np.uint64).reshape(n, self.words)
+        avg = _c(avg, np.float64).reshape(n)
+        front = _c(front, np.int32).reshape(self.V, ncj, nci)
+        vis = np.zeros((max(n, 1), self.words), np.uint64)
+        conf = np.zeros(max(n, 1), np.int64)
+        keep = np.zeros(max(n, 1), np.uint8)
+        rc = load().mvs_wfilt_test(self._h, n, _p(c, _dp), _p(nrm, _dp), _p(ref, _i32p), _p(mask, _u64p),
+                                   _p(avg, _dp), int(cell_size), float(adj_px), int(min_views), _p(front, _i32p),
+                                   _p(vis, _u64p), _p(conf, _i64p), _p(keep, _u8p))
+        check(rc, self._h, "mvs_wfilt_test")
+        return vis[:n], conf[:n], keep[:n]
+
+    def filter_warped(self, patches, cell_size=2, adj_px=2.0, min_views=3, passes=2, timer=None):
+        """Remove the patches of a warped patch set that contradict the
+        visibility of the rest (the definition is in include/mvs_amd.h).
+        `patches` is the dict expand_warped returns; it needs c, nrm, ref, mask,
+        avg and cell.  Each pass builds the front grid of the rows still alive
+        (wfilt_front_device), runs the test (wfilt_test_device) and sets the
+        removed rows' ref to -1 on the device; nothing is compacted between
+        passes.  It stops after `passes` passes or when a pass removes nothing.
+        Everything runs on the context's torch side stream; the host reads one
+        counter per pass, the survivors.
+
+        Returns a dict of numpy arrays: the surviving rows of every per-patch
+        array of the input (parent keeps the input's numbering), index (their
+        rows in the input), keep (over the input), vis (words uint64) and conf
+        (int64) of the last pass over the input, removed (per pass), front and
+        zfront (V,ncj,nci) rebuilt from the survivors, and occ (V,ncj,nci): the
+        survivors' cells through wexp_mark_device with the jobs (-1, ref, cell).
+        timer: an optional callable timer(phase, pass) called on the chain's
+        stream before each phase and with phase "end" after the last."""
+        import torch
+        for k in ("c", "nrm", "ref", "mask", "avg", "cell"):
+            if k not in patches:
+                raise RuntimeError(f"filter_warped: patches has no '{k}'")
+        ref0 = _c(patches["ref"], np.int32).reshape(-1)
+        n = len(ref0)
+        V, words = self.V, self.words
+        s = int(cell_size)
+        nci, ncj = self.cell_grid(s)
+        passes = int(passes)
+        if passes < 0:
+            raise RuntimeError("filter_warped: passes < 0")
+        c0 = _c(patches["c"], np.float64).reshape(n, 3)
+        n0 = _c(patches["nrm"], np.float64).reshape(n, 3)
+        m0 = _c(patches["mask"], np.uint64).reshape(n, words)
+        a0 = _c(patches["avg"], np.float64).reshape(n)
+        cell0 = _c(patches["cell"], np.int32).reshape(n, 2)
+        dev = torch.device(f"cuda:{self.device}")
+        st = self._side_stream()
+        sh = st.cuda_stream
+        tick = timer if timer is not None else (lambda phase, k: None)
+        removed = []
+        alive = int(((ref0 >= 0) & (ref0 < V)).sum())
+        with torch.cuda.stream(st):
+            c, nrm, ref, avg = (torch.from_numpy(x).to(dev) for x in (c0, n0, ref0.copy(), a0))
+            mask = torch.from_numpy(m0.view(np.int64)).to(dev)
+            front = torch.empty((V, ncj, nci), dtype=torch.int32, device=dev)
+            zfront = torch.empty((V, ncj, nci), dtype=torch.float64, device=dev)
+            vis = torch.zeros((n, words), dtype=torch.int64, device=dev)
+            conf = torch.zeros(n, dtype=torch.int64, device=dev)
+            keep = torch.empty(n, dtype=torch.uint8, device=dev)
+            for k in range(passes):
+                tick("front", k)
+                self.wfilt_front_device(c, ref, mask, s, front, zfront, stream=sh)
+                tick("test", k)
+                self.wfilt_test_device(c, nrm, ref, mask, avg, s, adj_px, min_views, front, vis, conf, keep, stream=sh)
+                ref.masked_fill_(keep == 0, -1)
+                tick("sync", k)
+                left = int(keep.sum().item())   # the pass's one read
+                removed.append(alive - left)
+                alive = left
+                if removed[-1] == 0:
+                    break
+            tick("rebuild", passes)
+            self.wfilt_front_device(c, ref, mask, s, front, zfront, stream=sh)
+            tick("occ", passes)
+            live = ((ref >= 0) & (ref < V)).to(torch.uint8)
+            job = torch.cat([torch.full((n, 1), -1, dtype=torch.int32, device=dev), ref.reshape(n, 1),
+                             torch.from_numpy(cell0).to(dev)], 1).contiguous()
+            occ = torch.zeros((V, ncj, nci), dtype=torch.uint8, device=dev)
+            self.wexp_mark_device(job, live, c, ref, mask, s, occ, stream=sh)
+            tick("end", passes)
+            h_keep = live.cpu().numpy()
+            res = {"keep": h_keep, "vis": vis.cpu().numpy().view(np.uint64), "conf": conf.cpu().numpy(),
+                   "front": front.cpu().numpy(), "zfront": zfront.cpu().numpy(), "occ": occ.cpu().numpy()}
+        st.synchronize()
+        index = np.flatnonzero(h_keep).astype(np.int64)
+        out = {k: np.asarray(v)[index] for k, v in patches.items()
+               if k not in ("occ", "trace") and isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == n}
+        out.update(res)
+        out["index"] = index
+        out["removed"] = removed
+        return out
 
     def pack_accepted(self, offset, count, mask, vlb, out, stream=None, c=None):
         """mvs_pack_accepted: the accepted candidates (count >= vlb) of a scored

@@ -331,6 +331,9 @@ struct mvs_ctx {
     DevBuf<int4> x_job;
     DevBuf<double> x_score;
     DevBuf<uint8_t> x_flags;
+    // the host-pointer filter calls' buffer (mvs_wfilt_front, mvs_wfilt_test):
+    // every array in 8-byte words; the device calls keep no state at all
+    DevBuf<int64_t> q_buf;
     // tiled scorer scratch
     DevBuf<int32_t> t_tiles, t_cand;
     // mvs_pack_accepted: the pack's row counter and chunk ticket (k_acc_pack
@@ -2095,6 +2098,157 @@ int mvs_wexp_mark_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const ui
         a.cell_size = cell_size;
         a.occ = d_occ;
         if (mvs_launch_wexp_mark(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wexp_mark launch failed"};
+        return 0;
+    });
+}
+
+// ---- the visibility-consistency filter (mvs_filter_warp.hip) ----
+
+static int wfilt_check(mvs_ctx* ctx, const char* who, int64_t n, int cell_size, double adj_px, int min_views,
+                       bool grids_ok, bool rows_ok) {
+    const std::string w(who);
+    if (n < 0) return set_err(ctx, Fail{MVS_E_ARG, w + ": n < 0"});
+    if (n >= ((int64_t)1 << 31)) return set_err(ctx, Fail{MVS_E_ARG, w + ": n must be below 2^31"});
+    if (cell_size < 1 || cell_size > 16) return set_err(ctx, Fail{MVS_E_ARG, w + ": cell_size must be in 1..16"});
+    if (!(adj_px >= 0.0 && adj_px < HUGE_VAL)) return set_err(ctx, Fail{MVS_E_ARG, w + ": adj_px must be finite and >= 0"});
+    if (min_views < 0) return set_err(ctx, Fail{MVS_E_ARG, w + ": min_views < 0"});
+    if (!grids_ok || (n > 0 && !rows_ok)) return set_err(ctx, Fail{MVS_E_ARG, w + ": null pointer"});
+    return 0;
+}
+
+static void wfilt_front_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref,
+                               const uint64_t* d_mask, int cell_size, int32_t* d_front, double* d_zfront,
+                               hipStream_t s) {
+    WfiltArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.cell_size = cell_size;
+    a.front = d_front;
+    a.zfront = (uint64_t*)d_zfront;
+    if (mvs_launch_wfilt_front(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wfilt_front launch failed"};
+}
+
+static void wfilt_test_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                              const uint64_t* d_mask, const double* d_avg, int cell_size, double adj_px,
+                              int min_views, const int32_t* d_front, uint64_t* d_vis, int64_t* d_conf,
+                              uint8_t* d_keep, hipStream_t s) {
+    WfiltArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.avg = d_avg;
+    a.cell_size = cell_size;
+    a.adj_px = adj_px;
+    a.min_views = min_views;
+    a.front = const_cast<int32_t*>(d_front);   // read only by the test's kernels
+    a.vis = d_vis;
+    a.conf = d_conf;
+    a.keep = d_keep;
+    if (mvs_launch_wfilt_test(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wfilt_test launch failed"};
+}
+
+int mvs_wfilt_front_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref, const uint64_t* d_mask,
+                           int cell_size, int32_t* d_front, double* d_zfront, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_front", n, cell_size, 0.0, 0, d_front && d_zfront,
+                             d_c && d_ref && d_mask))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wfilt_front_launch(ctx, n, d_c, d_ref, d_mask, cell_size, d_front, d_zfront, s);
+        return 0;
+    });
+}
+
+int mvs_wfilt_test_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                          const uint64_t* d_mask, const double* d_avg, int cell_size, double adj_px, int min_views,
+                          const int32_t* d_front, uint64_t* d_vis, int64_t* d_conf, uint8_t* d_keep, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_test", n, cell_size, adj_px, min_views, true,
+                             d_c && d_nrm && d_ref && d_mask && d_avg && d_front && d_vis && d_conf && d_keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wfilt_test_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, d_avg, cell_size, adj_px, min_views, d_front, d_vis,
+                          d_conf, d_keep, s);
+        return 0;
+    });
+}
+
+// the host-pointer calls' arrays inside q_buf, in 8-byte words: c, nrm, avg,
+// mask, vis, conf (n rows each), zfront (cells), then ref, front and keep
+struct WfiltHost {
+    int64_t n, cells, words;
+    int64_t total() const { return n * (8 + 2 * words) + cells + (n + 1) / 2 + (cells + 1) / 2 + (n + 7) / 8; }
+    double* c(int64_t* b) const { return (double*)b; }
+    double* nrm(int64_t* b) const { return (double*)b + 3 * n; }
+    double* avg(int64_t* b) const { return (double*)b + 6 * n; }
+    uint64_t* mask(int64_t* b) const { return (uint64_t*)b + 7 * n; }
+    uint64_t* vis(int64_t* b) const { return mask(b) + n * words; }
+    int64_t* conf(int64_t* b) const { return (int64_t*)(vis(b) + n * words); }
+    double* zfront(int64_t* b) const { return (double*)(conf(b) + n); }
+    int32_t* ref(int64_t* b) const { return (int32_t*)(zfront(b) + cells); }
+    int32_t* front(int64_t* b) const { return (int32_t*)(zfront(b) + cells + (n + 1) / 2); }
+    uint8_t* keep(int64_t* b) const { return (uint8_t*)(zfront(b) + cells + (n + 1) / 2 + (cells + 1) / 2); }
+};
+
+int mvs_wfilt_front(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, const uint64_t* mask,
+                    int cell_size, int32_t* front, double* zfront) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_front", n, cell_size, 0.0, 0, front && zfront, c && ref && mask))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const WfiltHost h{n, (int64_t)ctx->V * (ctx->H / cell_size) * (ctx->W / cell_size), (ctx->V + 63) / 64};
+        ctx->q_buf.ensure(h.total());
+        int64_t* b = ctx->q_buf.p;
+        if (n) {
+            HIPCHK(hipMemcpyAsync(h.c(b), c, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h.ref(b), ref, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(h.mask(b), mask, n * h.words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        }
+        wfilt_front_launch(ctx, n, h.c(b), h.ref(b), h.mask(b), cell_size, h.front(b), h.zfront(b), s);
+        if (h.cells) {
+            HIPCHK(hipMemcpyAsync(front, h.front(b), h.cells * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(zfront, h.zfront(b), h.cells * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+int mvs_wfilt_test(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                   const uint64_t* mask, const double* avg, int cell_size, double adj_px, int min_views,
+                   const int32_t* front, uint64_t* vis, int64_t* conf, uint8_t* keep) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_test", n, cell_size, adj_px, min_views, true,
+                             c && nrm && ref && mask && avg && front && vis && conf && keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const WfiltHost h{n, (int64_t)ctx->V * (ctx->H / cell_size) * (ctx->W / cell_size), (ctx->V + 63) / 64};
+        for (int64_t k = 0; k < h.cells; ++k)
+            if (front[k] < -1 || front[k] >= n) throw Fail{MVS_E_ARG, "mvs_wfilt_test: front entry outside -1..n-1"};
+        ctx->q_buf.ensure(h.total());
+        int64_t* b = ctx->q_buf.p;
+        HIPCHK(hipMemcpyAsync(h.c(b), c, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.nrm(b), nrm, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.avg(b), avg, n * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.ref(b), ref, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.mask(b), mask, n * h.words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        if (h.cells) HIPCHK(hipMemcpyAsync(h.front(b), front, h.cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        wfilt_test_launch(ctx, n, h.c(b), h.nrm(b), h.ref(b), h.mask(b), h.avg(b), cell_size, adj_px, min_views,
+                          h.front(b), h.vis(b), h.conf(b), h.keep(b), s);
+        HIPCHK(hipMemcpyAsync(vis, h.vis(b), n * h.words * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(conf, h.conf(b), n * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(keep, h.keep(b), n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
         return 0;
     });
 }

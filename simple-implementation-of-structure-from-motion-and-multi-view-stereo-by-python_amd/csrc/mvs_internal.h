@@ -150,6 +150,26 @@ struct MarkArgs {
     uint8_t* occ;
 };
 
+// The visibility-consistency filter's two calls (mvs_filter_warp.hip; device
+// pointers).  The front grid belongs to the caller: zfront holds the bit
+// patterns of positive binary64 depths (+inf = empty), front the patch index
+// (-1 = empty); V*ncj*nci elements each.
+struct WfiltArgs {
+    int64_t n;
+    const double* c;        // n*3
+    const double* nrm;      // n*3 (unread by the front call)
+    const int32_t* ref;     // n; outside 0..V-1 = a dead row
+    const uint64_t* mask;   // n*words
+    const double* avg;      // n   (unread by the front call)
+    int cell_size, min_views;
+    double adj_px;
+    int32_t* front;
+    uint64_t* zfront;       // written by the front call only
+    uint64_t* vis;          // n*words
+    int64_t* conf;          // n
+    uint8_t* keep;          // n
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -342,6 +362,11 @@ int mvs_launch_refine_lists(const SceneDev* sc, const ListArgs* a, hipStream_t s
 int mvs_launch_wexp_children(const SceneDev* sc, const WexpArgs* a, hipStream_t s);
 int mvs_launch_wexp_claim(const ClaimArgs* a, hipStream_t s);
 int mvs_launch_wexp_mark(const SceneDev* sc, const MarkArgs* a, hipStream_t s);
+// the visibility-consistency filter (mvs_filter_warp.hip): front = k_wfilt_fill,
+// k_wfilt_front depth pass and index pass; test = conf to zero, k_wfilt_conflict,
+// k_wfilt_decide
+int mvs_launch_wfilt_front(const SceneDev* sc, const WfiltArgs* a, hipStream_t s);
+int mvs_launch_wfilt_test(const SceneDev* sc, const WfiltArgs* a, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

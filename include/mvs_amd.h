@@ -56,10 +56,18 @@ const char* mvs_last_error(const mvs_ctx* ctx);
 /* Copies the rotations the projection uses (V*9) -- for parity tests. */
 int mvs_ctx_rproj(const mvs_ctx* ctx, double* Rp);
 /* The device part of the scene setup again, from the resident RGB images:
- * the gray stack and its signed view-major copy (k_build_scene).  For
- * measuring a cold sweep (setup + scoring); stream-ordered (NULL = the
+ * the gray stack and its signed view-major copy (k_build_scene), and the
+ * window-moment tables built so far (k_moments).  For measuring a cold sweep
+ * (setup + scoring) and after mvs_ctx_set_images; stream-ordered (NULL = the
  * context's stream). */
 int mvs_ctx_rebuild(mvs_ctx* ctx, void* stream);
+/* Replaces the resident RGB images of views [first_view, first_view + n_views)
+ * by rgb (n_views*H*W*3 uint8, host), on the device and in the host copy the
+ * stage's colours come from.  Synchronous on the context's stream; no call of
+ * the context may be in flight on another stream.  The gray stack, its
+ * view-major copy and the window-moment tables still hold the old images
+ * until mvs_ctx_rebuild. */
+int mvs_ctx_set_images(mvs_ctx* ctx, int first_view, int n_views, const uint8_t* rgb);
 
 /* Batched MyPatch.photo_consistenecy_test (MVS2.py:62-77): for candidate i
  * with centre c[3i..3i+2] and reference view ref[i], project into ref[i]

@@ -501,8 +501,14 @@ int or_expand_candidate(const or_scene *S, const double *pc, const double *pn, c
     for (int q = 0; q < 3; q++) nX[q] = (O[q] - X[q]) / dist;
     long cy = (long)cc1, cx = (long)cc0;
     cy = cy < 0 ? cy + S->H : cy; cx = cx < 0 ? cx + S->W : cx;
-    const uint8_t *px = S->rgb + (((int64_t)v * S->H + cy) * S->W + cx) * 3;
-    color[0] = px[0]; color[1] = px[1]; color[2] = px[2];
+    /* a cell centre past the last row or column (a parent at the border): the
+     * reference's get_color raises IndexError there; the library's colour is
+     * 0 0 0, and so is this one (the read used to run into the next row) */
+    color[0] = color[1] = color[2] = 0;
+    if (cy >= 0 && cy < S->H && cx >= 0 && cx < S->W) {
+        const uint8_t *px = S->rgb + (((int64_t)v * S->H + cy) * S->W + cx) * 3;
+        color[0] = px[0]; color[1] = px[1]; color[2] = px[2];
+    }
     int32_t Vidx[OR_MAXV];
     double avg;
     int cnt = or_photo_test(S, X, v, thr, wid, Vidx, xy, &avg);

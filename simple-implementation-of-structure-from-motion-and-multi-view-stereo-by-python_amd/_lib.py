@@ -32,6 +32,7 @@ SIGNATURES = [
     ("mvs_ctx_destroy", None, [_vp]),
     ("mvs_ctx_rproj", ctypes.c_int, [_vp, _dp]),
     ("mvs_ctx_rebuild", ctypes.c_int, [_vp, _vp]),
+    ("mvs_ctx_set_images", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _u8p]),
     ("mvs_score", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, ctypes.c_int, ctypes.c_double,
                                  _dp, _u64p, _i32p, _dp]),
     ("mvs_score_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int,
@@ -333,6 +334,16 @@ class MvsContext:
         """Rebuild the device gray stack / view-major copy from the resident
         RGB images (stream-ordered; for cold-sweep timing)."""
         check(load().mvs_ctx_rebuild(self._h, stream), self._h, "mvs_ctx_rebuild")
+
+    def set_images(self, first_view, imgs):
+        """Replace the resident RGB images of views first_view, first_view + 1,
+        ... by imgs (k, H, W, 3) uint8 (mvs_ctx_set_images, synchronous).  The
+        gray stack and the moment tables follow at the next rebuild()."""
+        rgb = _c(imgs, np.uint8)
+        if rgb.ndim != 4 or rgb.shape[1:] != (self.H, self.W, 3):
+            raise RuntimeError(f"images must be (k,{self.H},{self.W},3) uint8 RGB, got {rgb.shape}")
+        check(load().mvs_ctx_set_images(self._h, int(first_view), len(rgb), _p(rgb, _u8p)), self._h,
+              "mvs_ctx_set_images")
 
     def kernel_timing(self, enable=True, every=1):
         """Start (reset) or stop HIP-event timing of the dominant scoring kernel;

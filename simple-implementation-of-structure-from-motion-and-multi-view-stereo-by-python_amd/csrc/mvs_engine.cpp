@@ -1553,6 +1553,20 @@ int mvs_ctx_rebuild(mvs_ctx* ctx, void* stream) {
     });
 }
 
+int mvs_ctx_set_images(mvs_ctx* ctx, int first_view, int n_views, const uint8_t* rgb) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    return guarded(ctx, [&]() {
+        if (first_view < 0 || n_views < 0 || first_view > ctx->V - n_views) throw Fail{MVS_E_ARG, "views out of range"};
+        if (n_views == 0) return 0;
+        if (!rgb) throw Fail{MVS_E_ARG, "null argument"};
+        const int64_t per = (int64_t)ctx->H * ctx->W * 3;
+        HIPCHK(hipMemcpyAsync(ctx->d_rgb.p + first_view * per, rgb, n_views * per, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        std::memcpy(ctx->h_rgb.data() + first_view * per, rgb, (size_t)(n_views * per));
+        return 0;
+    });
+}
+
 int mvs_ctx_rproj(const mvs_ctx* ctx, double* Rp) {
     if (!ctx || !Rp) return MVS_E_ARG;
     for (int v = 0; v < ctx->V; ++v) std::memcpy(Rp + 9 * v, ctx->cams[v].Rp, 9 * sizeof(double));

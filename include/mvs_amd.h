@@ -399,6 +399,51 @@ int mvs_wfilt_front(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref
 int mvs_wfilt_test(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
                    const uint64_t* mask, const double* avg, int cell_size, double adj_px, int min_views,
                    const int32_t* front, uint64_t* vis, int64_t* conf, uint8_t* keep);
+/* ---- Neighbour-support test for warped patch sets ----
+ * PMVS's third filter on the front grid: a patch stays when enough of the
+ * patches next to it, in the images it is seen in, lie on its surface.  One
+ * stream-ordered device call (k_wfilt_support); MvsContext.filter_warped runs it
+ * after the visibility passes when given min_support.  The patch set, T(p),
+ * placement, the front grid and adjacency are the visibility filter's above,
+ * unchanged; adj_px >= 0 (finite), min_support in [0, 1] (finite), min_neigh >= 0.
+ *   Incidences.  For a live patch p and every v in T(p) in which p is placed,
+ *   in cell (i, j): the eight cells (i + di, j + dj), di, dj in {-1, 0, 1}
+ *   without (0, 0), that lie inside the grid (0 <= i + di < nci, 0 <= j + dj <
+ *   ncj).  q = front[v][j + dj][i + di]; an entry outside -1..n-1 reads as -1.
+ *   q = -1 and q = p are skipped.  The grid is taken as given: the centre and
+ *   normal of a named row are read whether or not that row is alive, and the
+ *   grid need not come from the same rows.
+ *   N(p) (int32) = the number of the remaining incidences (v, di, dj).
+ *   A(p) (int32) = the number of those in which p and q are adjacent in view v:
+ *   d = c_p - c_q, |d.nrm_p| + |d.nrm_q| < 2 rho, rho = (adj_px z_p(v)) /
+ *   ((fx_v + fy_v) / 2), each operation in the visibility filter's order,
+ *   unfused; a nan anywhere makes them not adjacent.
+ *   Incidences are counted, not distinct patches: a front patch that fills
+ *   several neighbour cells, or the neighbour cells of several views, counts
+ *   once per cell and view.  N and A are plain integer sums.
+ *   Decision.  keep(p) = alive and N(p) >= min_neigh and (double)A(p) >=
+ *   min_support * (double)N(p), the product one binary64 multiply.
+ *   A dead row gets N = A = 0 and keep = 0.
+ * Only the front patch of a neighbour cell counts, not every patch that
+ * projects into it (PMVS's C(p) holds all of them).
+ * mvs_wfilt_support_device writes d_nb, d_adj (int32) and d_keep (uint8) of every
+ * row and nothing else; n = 0 returns MVS_OK and launches nothing.  One wave
+ * per patch, lane = view in groups of 64; the wave's sums come from cross-lane
+ * shuffles.  No atomics, no scratch and no context state: it may run on any
+ * stream beside any other call.  Results are deterministic.
+ * The host-pointer variant mvs_wfilt_support is synchronous, on the context's
+ * stream and a buffer of its own, and returns MVS_E_ARG for a front entry
+ * outside -1..n-1.
+ * MVS_E_ARG (message in mvs_last_error) for a scalar out of range (cell_size,
+ * adj_px negative, nan or inf, min_support nan or outside [0, 1], min_neigh <
+ * 0), a NULL pointer, n < 0 or n >= 2^31. */
+int mvs_wfilt_support_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm,
+                             const int32_t* d_ref, const uint64_t* d_mask, int cell_size, double adj_px,
+                             double min_support, int min_neigh, const int32_t* d_front, int32_t* d_nb,
+                             int32_t* d_adj, uint8_t* d_keep, void* stream);
+int mvs_wfilt_support(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                      const uint64_t* mask, int cell_size, double adj_px, double min_support, int min_neigh,
+                      const int32_t* front, int32_t* nb, int32_t* adj, uint8_t* keep);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

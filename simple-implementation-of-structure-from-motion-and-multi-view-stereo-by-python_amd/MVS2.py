@@ -142,6 +142,20 @@ def filter_patches_warped(ctx, patches, **kw):
     return ctx.filter_warped(patches, **kw)
 
 
+def resume_patches_warped(ctx, patches, rounds=2, cell_size=2, MIN_NCC=0.7, wid=5, min_cos=0.3, **kw):
+    """More rounds of the expansion from an existing warped patch set, e.g. the
+    survivors of filter_patches_warped (no reference counterpart; see
+    MvsContext.resume_warped, which takes the remaining keywords)."""
+    return ctx.resume_warped(patches, rounds, cell_size=cell_size, wid=wid, min_ncc=MIN_NCC, min_cos=min_cos, **kw)
+
+
+def reconstruct_patches_warped(ctx, centroids, normals, ref_views, **kw):
+    """The expand -> filter loop of the warped pipeline (no reference
+    counterpart; see MvsContext.reconstruct_warped, which takes the keywords):
+    the filtered patch set grown from the seed patches, and the loop's history."""
+    return ctx.reconstruct_warped(centroids, normals, ref_views, **kw)
+
+
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):
     """MVS2.py:176-295 on the GPU.  Returns None like the reference; the run's
     counters are left in MVS2.last_stats.

@@ -66,6 +66,11 @@ SIGNATURES = [
     ("mvs_wfilt_front", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _u64p, ctypes.c_int, _i32p, _dp]),
     ("mvs_wfilt_test", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, _u64p, _dp, ctypes.c_int,
                                       ctypes.c_double, ctypes.c_int, _i32p, _u64p, _i64p, _u8p]),
+    ("mvs_wfilt_support_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int,
+                                                ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                                _vp]),
+    ("mvs_wfilt_support", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, _u64p, ctypes.c_int, ctypes.c_double,
+                                         ctypes.c_double, ctypes.c_int, _i32p, _i32p, _i32p, _u8p]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -902,7 +907,6 @@ class MvsContext:
         winners' refined patches, in winner order) and occ after marking.
         timer: an optional callable timer(phase, round) called on the chain's
         stream before each phase and with phase "end" after the last."""
-        import torch
         c = _c(c, np.float64).reshape(-1, 3)
         nrm = _c(nrm, np.float64).reshape(-1, 3)
         ref = _c(ref, np.int32).reshape(-1)
@@ -916,23 +920,9 @@ class MvsContext:
         nci, ncj = self.cell_grid(s)
         if refine_levels and not 1 <= int(max_views) <= 32:
             raise RuntimeError("expand_warped: max_views must be in 1..32")
-        V, words = self.V, self.words
         Rp, K, t = self.rproj(), self._K, self._t
         if max_dist is None and n0:
             max_dist = 2.0 * s * float(self.refine_depth_steps(c[:1], ref[:1], 1.0)[0])
-        dev = torch.device(f"cuda:{self.device}")
-        f64 = dict(dtype=torch.float64, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        i64 = dict(dtype=torch.int64, device=dev)
-        u8 = dict(dtype=torch.uint8, device=dev)
-        st = self._side_stream()
-        sh = st.cuda_stream
-        tick = timer if timer is not None else (lambda phase, rnd: None)
-        want_ncc = trace or refine_levels > 0
-        keys = ("c", "nrm", "ref", "mask", "count", "avg", "round", "parent", "cell")
-        out = {k: [] for k in keys}
-        traces = []
-        total, base = 0, 0
         # round 0 on the host: the seeds' cells (the library's projection, in Python floats)
         jobs0 = np.full((n0, 4), -1, np.int32)
         inside0 = np.zeros(n0, np.uint8)
@@ -950,14 +940,78 @@ class MvsContext:
             if z > 0 and 0 <= x < self.W and 0 <= y < self.H and int(x) // s < nci and int(y) // s < ncj:
                 jobs0[k, 2:] = (int(x) // s, int(y) // s)
                 inside0[k] = 1
+        return self._wexp_chain(rounds, (c, nrm, ref, jobs0, inside0), None, s, wid, min_ncc, min_cos, vlb, max_dist,
+                                refine_levels, max_views, depth_px, max_patches, trace, timer)
+
+    def _wexp_chain(self, rounds, seeds, start, s, wid, min_ncc, min_cos, vlb, max_dist, refine_levels, max_views,
+                    depth_px, max_patches, trace, timer):
+        """The rounds of expand_warped (seeds = (c, nrm, ref, jobs, inside) of
+        round 0, start None) and of resume_warped (seeds None, start = the host
+        arrays of an existing set and its occ or None).  From a set, the
+        frontier of every round is the whole current set in row order and the
+        first round's children cost one more counter read."""
+        import torch
+        V, words = self.V, self.words
+        nci, ncj = self.cell_grid(s)
+        dev = torch.device(f"cuda:{self.device}")
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        i64 = dict(dtype=torch.int64, device=dev)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        st = self._side_stream()
+        sh = st.cuda_stream
+        tick = timer if timer is not None else (lambda phase, rnd: None)
+        want_ncc = trace or refine_levels > 0
+        keys = ("c", "nrm", "ref", "mask", "count", "avg", "round", "parent", "cell")
+        out = {k: [] for k in keys}
+        traces = []
+        total, base, r0 = 0, 0, 0
+        S = None   # from a set: its c, nrm, ref and mask on the device, every round's winners appended
         with torch.cuda.stream(st):
-            occ = torch.zeros((V, ncj, nci), **u8)
-            job = torch.from_numpy(jobs0).to(dev)
-            cc, cn, cref = (torch.from_numpy(x).to(dev) for x in (c, nrm, ref))
-            inside = torch.from_numpy(inside0).to(dev)
             counters = torch.zeros(2, **i64)   # [the next round's job total, this round's winners]
-            m = n0
-            for rnd in range(rounds):
+
+            def children(F, cap):
+                nb = [torch.empty((cap, 4), **i32), torch.empty((cap, 3), **f64), torch.empty((cap, 3), **f64),
+                      torch.empty(cap, **i32)]
+                self.wexp_children_device(F[0], F[1], F[2], F[3], s, occ, max_dist, nb[0], nb[1], nb[2], nb[3],
+                                          counters[:1], stream=sh)
+                return nb
+
+            if start is None:
+                c, nrm, ref, jobs0, inside0 = seeds
+                occ = torch.zeros((V, ncj, nci), **u8)
+                job = torch.from_numpy(jobs0).to(dev)
+                cc, cn, cref = (torch.from_numpy(x).to(dev) for x in (c, nrm, ref))
+                inside = torch.from_numpy(inside0).to(dev)
+                m = len(ref)
+            else:
+                host, occ0 = start
+                for k in keys:
+                    x = host[k].view(np.int64) if k == "mask" else host[k]
+                    out[k].append(torch.from_numpy(x).to(dev))
+                S = [out[k][0] for k in ("c", "nrm", "ref", "mask")]
+                total = len(host["ref"])
+                r0 = int(host["round"].max()) + 1 if total else 0
+                if occ0 is not None:
+                    occ = torch.from_numpy(occ0).to(dev)
+                else:   # the set's cells, as filter_warped marks them
+                    occ = torch.zeros((V, ncj, nci), **u8)
+                    job = torch.cat([torch.full((total, 1), -1, **i32), S[2].reshape(total, 1), out["cell"][0]],
+                                    1).contiguous()
+                    self.wexp_mark_device(job, torch.ones(total, **u8), S[0], S[2], S[3], s, occ, stream=sh)
+                inside = None
+                m = 0
+                if rounds > 0 and total and (max_patches is None or total < int(max_patches)):
+                    tick("children", r0 - 1)
+                    cap = min(4 * V * total, max(1 << 20, 16 * total))
+                    nb = children(S, cap)
+                    tot = int(counters[0].item())   # the first round's job total
+                    if tot > cap:
+                        cap = tot
+                        nb = children(S, cap)
+                    m = min(tot, cap)
+                    job, cc, cn, cref = (x[:m].contiguous() for x in nb)
+            for rnd in range(r0, r0 + rounds):
                 if m == 0:
                     break
                 tick("score", rnd)
@@ -1018,27 +1072,25 @@ class MvsContext:
                     traces.append(tr)
                 # the next round's children from every job: a job that did not win gets
                 # no view (ref -1, empty mask), so the order is the winners' order
-                last = rnd + 1 >= rounds
+                last = rnd + 1 >= r0 + rounds
                 winb = win.bool()
                 counters[1] = win.sum()
                 if not last:
                     tick("children", rnd)
                     f_ref = torch.where(winb, cref, torch.full_like(cref, -1))
                     f_mask = mask * winb.to(torch.int64)[:, None]
-                    cap = min(4 * V * m, max(1 << 20, 16 * m))
-                    nb = [torch.empty((cap, 4), **i32), torch.empty((cap, 3), **f64), torch.empty((cap, 3), **f64),
-                          torch.empty(cap, **i32)]
-                    self.wexp_children_device(cc, cn, f_ref, f_mask, s, occ, max_dist, nb[0], nb[1], nb[2], nb[3],
-                                              counters[:1], stream=sh)
+                    F = [cc, cn, f_ref, f_mask]
+                    if S is not None:   # the whole set first, then this round's jobs
+                        F = [torch.cat([x, y]) for x, y in zip(S, F)]
+                    nf = int(F[2].numel())
+                    cap = min(4 * V * nf, max(1 << 20, 16 * nf))
+                    nb = children(F, cap)
                 tick("sync", rnd)
                 tot, nw = (int(x) for x in counters.cpu())   # the round's one read
                 if not last and tot > cap and nw and (max_patches is None or total + nw < max_patches):
                     # more jobs than the first guess holds: the same call again with room for all
                     cap = tot
-                    nb = [torch.empty((cap, 4), **i32), torch.empty((cap, 3), **f64), torch.empty((cap, 3), **f64),
-                          torch.empty(cap, **i32)]
-                    self.wexp_children_device(cc, cn, f_ref, f_mask, s, occ, max_dist, nb[0], nb[1], nb[2], nb[3],
-                                              counters[:1], stream=sh)
+                    nb = children(F, cap)
                 tick("append", rnd)
                 if nw == 0:
                     break
@@ -1047,16 +1099,23 @@ class MvsContext:
                 out["mask"].append(mask[winb]); out["count"].append(count[winb]); out["avg"].append(avg[winb])
                 out["round"].append(torch.full((nw,), rnd, **i32))
                 par = job[winb, 0].to(torch.int64)
-                out["parent"].append(torch.where(par >= 0, par + base, par))
+                # from a set the parent already is a row of the set (the remapping below)
+                out["parent"].append(torch.where(par >= 0, par + base, par) if S is None else par)
                 out["cell"].append(job[winb, 2:])
                 base, total = total, total + nw
                 if last or (max_patches is not None and total >= int(max_patches)):
                     break
                 m = min(tot, cap)
                 job, cc, cn, cref = (x[:m].contiguous() for x in nb)
-                job[:, 0] = rank[job[:, 0].long()].to(torch.int32)   # parent: job index -> index among the winners
+                j0 = job[:, 0].long()
+                if S is None:
+                    job[:, 0] = rank[j0].to(torch.int32)   # parent: job index -> index among the winners
+                else:
+                    # parent: a row of the set as it is, a job index -> the winner's row behind the set
+                    job[:, 0] = torch.where(j0 < base, j0, base + rank[(j0 - base).clamp(min=0)]).to(torch.int32)
+                    S = [torch.cat([x, out[k][-1]]) for x, k in zip(S, ("c", "nrm", "ref", "mask"))]
                 inside = None
-            tick("end", rounds)
+            tick("end", r0 + rounds)
             empty = {"c": torch.empty((0, 3), **f64), "nrm": torch.empty((0, 3), **f64), "ref": torch.empty(0, **i32),
                      "mask": torch.empty((0, words), **i64), "count": torch.empty(0, **i32),
                      "avg": torch.empty(0, **f64), "round": torch.empty(0, **i32), "parent": torch.empty(0, **i64),
@@ -1074,6 +1133,69 @@ class MvsContext:
                 res["trace"] = [host(tr) for tr in traces]
         st.synchronize()
         return res
+
+    def resume_warped(self, patches, rounds, cell_size=2, wid=5, min_ncc=0.7, min_cos=0.3, vlb=2, max_dist=None,
+                      refine_levels=0, max_views=8, depth_px=1.0, max_patches=None, trace=False, timer=None):
+        """Grow an existing patch set by `rounds` more rounds of expand_warped's
+        expansion.  `patches` is a dict as expand_warped or filter_warped
+        returns it; it needs c, nrm, ref, mask, count, avg, round, parent and
+        cell.  Every row must be alive (ref in 0..V-1) and every cell inside the
+        grid of cell_size.  occ is patches["occ"] when that has the shape
+        (V,ncj,nci); otherwise it is rebuilt from the rows (wexp_mark_device
+        with the jobs (-1, ref, cell), as filter_warped does).  max_dist: the
+        argument, else patches["max_dist"], else expand_warped's rule on the
+        first row.
+
+        No row of the input is scored again.  The frontier of every round is
+        the whole current set in row order, the input first; its children
+        (wexp_children_device) are the round's candidates, and the round is an
+        expand_warped round from there: score, accept, claim, optional
+        refinement, mark.  An older patch's vacant neighbours are the candidates
+        that failed before; they fail again and compete for nothing, so
+        resuming k rounds from the set of R rounds gives the set of R + k
+        rounds.  The host reads the same two counters once per round, and the
+        first round's job total once more.  It stops after `rounds` rounds, at
+        a round with no job or no winner, or at max_patches, which counts the
+        input.
+
+        Returns expand_warped's dict: the input rows unchanged, then the new
+        rows (parent indexes the returned set, round continues from the
+        input's highest + 1), occ and max_dist.  rounds = 0 returns the input
+        with its occ."""
+        keys = ("c", "nrm", "ref", "mask", "count", "avg", "round", "parent", "cell")
+        for k in keys:
+            if k not in patches:
+                raise RuntimeError(f"resume_warped: patches has no '{k}'")
+        rounds, refine_levels, vlb = int(rounds), int(refine_levels), int(vlb)
+        if rounds < 0:
+            raise RuntimeError("resume_warped: rounds < 0")
+        if refine_levels and not 1 <= int(max_views) <= 32:
+            raise RuntimeError("resume_warped: max_views must be in 1..32")
+        s = int(cell_size)
+        nci, ncj = self.cell_grid(s)
+        ref = _c(patches["ref"], np.int32).reshape(-1)
+        n = len(ref)
+        host = {"c": _c(patches["c"], np.float64).reshape(n, 3), "nrm": _c(patches["nrm"], np.float64).reshape(n, 3),
+                "ref": ref, "mask": _c(patches["mask"], np.uint64).reshape(n, self.words),
+                "count": _c(patches["count"], np.int32).reshape(n), "avg": _c(patches["avg"], np.float64).reshape(n),
+                "round": _c(patches["round"], np.int32).reshape(n),
+                "parent": _c(patches["parent"], np.int64).reshape(n),
+                "cell": _c(patches["cell"], np.int32).reshape(n, 2)}
+        if n and (ref.min() < 0 or ref.max() >= self.V):
+            raise RuntimeError("resume_warped: a row is dead (ref outside 0..V-1)")
+        cell = host["cell"]
+        if n and (cell.min() < 0 or cell[:, 0].max() >= nci or cell[:, 1].max() >= ncj):
+            raise RuntimeError("resume_warped: a cell lies outside the grid")
+        occ = patches.get("occ")
+        if occ is not None:
+            occ = np.asarray(occ)
+            occ = _c(occ, np.uint8) if occ.shape == (self.V, ncj, nci) else None
+        if max_dist is None:
+            max_dist = patches.get("max_dist")
+        if max_dist is None and n:
+            max_dist = 2.0 * s * float(self.refine_depth_steps(host["c"][:1], ref[:1], 1.0)[0])
+        return self._wexp_chain(rounds, None, (host, occ), s, wid, min_ncc, min_cos, vlb, max_dist, refine_levels,
+                                max_views, depth_px, max_patches, trace, timer)
 
     # ---- visibility-consistency filter of a warped patch set ----
 
@@ -1149,7 +1271,46 @@ class MvsContext:
         check(rc, self._h, "mvs_wfilt_test")
         return vis[:n], conf[:n], keep[:n]
 
-    def filter_warped(self, patches, cell_size=2, adj_px=2.0, min_views=3, passes=2, timer=None):
+    def wfilt_support_device(self, c, nrm, ref, mask, cell_size, adj_px, min_support, min_neigh, front, nb, adj, keep,
+                             stream=None):
+        """mvs_wfilt_support_device on torch device tensors (contiguous: c, nrm
+        float64 (n,3), ref int32 (n,), mask int64 (n,words), front int32
+        (V,ncj,nci), nb and adj int32 (n,), keep uint8 (n,)); stream-ordered."""
+        n = int(ref.numel())
+        nci, ncj = self.cell_grid(cell_size)
+        for name, x, size, shape in [("c", c, 8, (n, 3)), ("nrm", nrm, 8, (n, 3)), ("ref", ref, 4, (n,)),
+                                     ("mask", mask, 8, (n, self.words)), ("front", front, 4, (self.V, ncj, nci)),
+                                     ("nb", nb, 4, (n,)), ("adj", adj, 4, (n,)), ("keep", keep, 1, (n,))]:
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wfilt_support_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wfilt_support_device(self._h, n, c.data_ptr(), nrm.data_ptr(), ref.data_ptr(), mask.data_ptr(),
+                                             int(cell_size), float(adj_px), float(min_support), int(min_neigh),
+                                             front.data_ptr(), nb.data_ptr(), adj.data_ptr(), keep.data_ptr(),
+                                             self._stream_handle(stream))
+        check(rc, self._h, "mvs_wfilt_support_device")
+
+    def wfilt_support(self, c, nrm, ref, mask, cell_size, adj_px, min_support, min_neigh, front):
+        """The neighbour-support test of a patch set against a front grid
+        (mvs_wfilt_support, host pointers; a front entry outside -1..n-1 raises).
+        Returns nb (n,) int32, adj (n,) int32 and keep (n,) uint8."""
+        nci, ncj = self.cell_grid(cell_size)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        c = _c(c, np.float64).reshape(n, 3)
+        nrm = _c(nrm, np.float64).reshape(n, 3)
+        mask = _c(mask, np.uint64).reshape(n, self.words)
+        front = _c(front, np.int32).reshape(self.V, ncj, nci)
+        nb = np.zeros(max(n, 1), np.int32)
+        adj = np.zeros(max(n, 1), np.int32)
+        keep = np.zeros(max(n, 1), np.uint8)
+        rc = load().mvs_wfilt_support(self._h, n, _p(c, _dp), _p(nrm, _dp), _p(ref, _i32p), _p(mask, _u64p),
+                                      int(cell_size), float(adj_px), float(min_support), int(min_neigh),
+                                      _p(front, _i32p), _p(nb, _i32p), _p(adj, _i32p), _p(keep, _u8p))
+        check(rc, self._h, "mvs_wfilt_support")
+        return nb[:n], adj[:n], keep[:n]
+
+    def filter_warped(self, patches, cell_size=2, adj_px=2.0, min_views=3, passes=2, timer=None, min_support=None,
+                      min_neigh=1, support_passes=1):
         """Remove the patches of a warped patch set that contradict the
         visibility of the rest (the definition is in include/mvs_amd.h).
         `patches` is the dict expand_warped returns; it needs c, nrm, ref, mask,
@@ -1159,6 +1320,15 @@ class MvsContext:
         passes.  It stops after `passes` passes or when a pass removes nothing.
         Everything runs on the context's torch side stream; the host reads one
         counter per pass, the survivors.
+
+        min_support not None: after the visibility passes, up to support_passes
+        passes of the neighbour-support test (wfilt_support_device with adj_px,
+        min_support and min_neigh) in the same way: the front grid of the rows
+        still alive, the test, ref = -1 for the removed rows, one counter read;
+        they stop when a pass removes nothing.  The dict then also holds nb and
+        adj (int32, the last support pass over the input; zeros when none ran)
+        and removed_support (per support pass).  The timer's phases of a
+        support pass are "sfront", "support" and "ssync".
 
         Returns a dict of numpy arrays: the surviving rows of every per-patch
         array of the input (parent keeps the input's numbering), index (their
@@ -1180,6 +1350,9 @@ class MvsContext:
         passes = int(passes)
         if passes < 0:
             raise RuntimeError("filter_warped: passes < 0")
+        support_passes = int(support_passes) if min_support is not None else 0
+        if support_passes < 0:
+            raise RuntimeError("filter_warped: support_passes < 0")
         c0 = _c(patches["c"], np.float64).reshape(n, 3)
         n0 = _c(patches["nrm"], np.float64).reshape(n, 3)
         m0 = _c(patches["mask"], np.uint64).reshape(n, words)
@@ -1211,6 +1384,26 @@ class MvsContext:
                 alive = left
                 if removed[-1] == 0:
                     break
+            if min_support is not None:
+                removed_support = []
+                nb = torch.zeros(n, dtype=torch.int32, device=dev)
+                adj = torch.zeros(n, dtype=torch.int32, device=dev)
+                if support_passes == 0 or n == 0:   # no pass runs the call: its scalar checks all the same
+                    self.wfilt_support_device(c[:0], nrm[:0], ref[:0], mask[:0], s, adj_px, min_support, min_neigh,
+                                              front, nb[:0], adj[:0], keep[:0], stream=sh)
+                for k in range(support_passes):
+                    tick("sfront", k)
+                    self.wfilt_front_device(c, ref, mask, s, front, zfront, stream=sh)
+                    tick("support", k)
+                    self.wfilt_support_device(c, nrm, ref, mask, s, adj_px, min_support, min_neigh, front, nb, adj,
+                                              keep, stream=sh)
+                    ref.masked_fill_(keep == 0, -1)
+                    tick("ssync", k)
+                    left = int(keep.sum().item())   # the pass's one read
+                    removed_support.append(alive - left)
+                    alive = left
+                    if removed_support[-1] == 0:
+                        break
             tick("rebuild", passes)
             self.wfilt_front_device(c, ref, mask, s, front, zfront, stream=sh)
             tick("occ", passes)
@@ -1223,6 +1416,8 @@ class MvsContext:
             h_keep = live.cpu().numpy()
             res = {"keep": h_keep, "vis": vis.cpu().numpy().view(np.uint64), "conf": conf.cpu().numpy(),
                    "front": front.cpu().numpy(), "zfront": zfront.cpu().numpy(), "occ": occ.cpu().numpy()}
+            if min_support is not None:
+                res.update({"nb": nb.cpu().numpy(), "adj": adj.cpu().numpy(), "removed_support": removed_support})
         st.synchronize()
         index = np.flatnonzero(h_keep).astype(np.int64)
         out = {k: np.asarray(v)[index] for k, v in patches.items()
@@ -1231,6 +1426,65 @@ class MvsContext:
         out["index"] = index
         out["removed"] = removed
         return out
+
+    @staticmethod
+    def renumber_parents(parent, index, n):
+        """The parents of the rows `index` (ascending) of an n-row set in the
+        numbering of those rows alone: a removed parent becomes -2, a seed's -1
+        and an earlier -2 stay."""
+        parent = np.asarray(parent, np.int64)
+        new = np.full(n + 1, -2, np.int64)        # the last element serves the negative parents
+        new[np.asarray(index, np.int64)] = np.arange(len(index))
+        return np.where(parent >= 0, new[np.where(parent >= 0, parent, n)], parent)
+
+    def reconstruct_warped(self, c, nrm, ref, iterations=3, rounds=4, resume_rounds=2, expand=None, filter=None,
+                           start=None, timer=None):
+        """PMVS's expand -> filter loop on the warped pipeline: expand_warped of
+        the seeds (c, nrm, ref) for `rounds` rounds, then `iterations` times
+        filter_warped and, unless it was the last filter, resume_warped for
+        resume_rounds rounds from the survivors and their occ.  `expand` holds
+        the keywords of expand_warped and resume_warped, `filter` those of
+        filter_warped; cell_size is shared (give it in `expand`).  After every
+        filter the survivors' parent is renumbered through index
+        (renumber_parents).  start: an existing set (a dict as resume_warped
+        takes it, with max_dist) to loop on in place of the seeds' expansion;
+        c, nrm, ref and rounds are then unused.  timer: an optional callable
+        timer(stage, iteration, phase, k) that receives the phase marks of every
+        stage ("expand", "filter", "resume") as that stage's own timer would.
+
+        Returns the last filter_warped's dict with parent renumbered, max_dist,
+        and history: per iteration a dict of patches (the set's size before the
+        filter), removed, removed_support and resumed (the size after the
+        resumption, None after the last filter)."""
+        expand, filt = dict(expand or {}), dict(filter or {})
+        for k in ("trace", "timer"):
+            if k in expand or k in filt:
+                raise RuntimeError(f"reconstruct_warped: '{k}' belongs to the single calls")
+
+        def stage(name, it):   # the stages' phase marks, told apart
+            return None if timer is None else (lambda phase, k: timer(name, it, phase, k))
+
+        if filt.setdefault("cell_size", expand.get("cell_size", 2)) != expand.get("cell_size", 2):
+            raise RuntimeError("reconstruct_warped: expand and filter disagree on cell_size")
+        iterations = int(iterations)
+        if iterations < 1:
+            raise RuntimeError("reconstruct_warped: iterations < 1")
+        ps = start if start is not None else self.expand_warped(c, nrm, ref, rounds, timer=stage("expand", 0),
+                                                                **expand)
+        grow = dict(expand, max_dist=ps["max_dist"])
+        history = []
+        for it in range(iterations):
+            before = len(ps["ref"])
+            ps = self.filter_warped(ps, timer=stage("filter", it), **filt)
+            ps["parent"] = self.renumber_parents(ps["parent"], ps["index"], before)
+            history.append({"patches": before, "removed": ps["removed"],
+                            "removed_support": ps.get("removed_support", []), "resumed": None})
+            if it + 1 < iterations:
+                ps = self.resume_warped(ps, resume_rounds, timer=stage("resume", it), **grow)
+                history[-1]["resumed"] = len(ps["ref"])
+        ps["max_dist"] = grow["max_dist"]
+        ps["history"] = history
+        return ps
 
     def pack_accepted(self, offset, count, mask, vlb, out, stream=None, c=None):
         """mvs_pack_accepted: the accepted candidates (count >= vlb) of a scored

@@ -2267,6 +2267,101 @@ int mvs_wfilt_test(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, 
     });
 }
 
+// ---- the neighbour-support test (k_wfilt_support) ----
+
+static int wsup_check(mvs_ctx* ctx, int64_t n, int cell_size, double adj_px, double min_support, int min_neigh,
+                      bool rows_ok) {
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_support", n, cell_size, adj_px, 0, true, rows_ok)) return rc;
+    if (!(min_support >= 0.0 && min_support <= 1.0))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wfilt_support: min_support must be in 0..1"});
+    if (min_neigh < 0) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wfilt_support: min_neigh < 0"});
+    return 0;
+}
+
+static void wsup_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                        const uint64_t* d_mask, int cell_size, double adj_px, double min_support, int min_neigh,
+                        const int32_t* d_front, int32_t* d_nb, int32_t* d_adj, uint8_t* d_keep, hipStream_t s) {
+    WsupArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.cell_size = cell_size;
+    a.min_neigh = min_neigh;
+    a.adj_px = adj_px;
+    a.min_support = min_support;
+    a.front = d_front;
+    a.nb = d_nb;
+    a.adj = d_adj;
+    a.keep = d_keep;
+    if (mvs_launch_wfilt_support(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wfilt_support launch failed"};
+}
+
+int mvs_wfilt_support_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                             const uint64_t* d_mask, int cell_size, double adj_px, double min_support,
+                             int min_neigh, const int32_t* d_front, int32_t* d_nb, int32_t* d_adj, uint8_t* d_keep,
+                             void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wsup_check(ctx, n, cell_size, adj_px, min_support, min_neigh,
+                            d_c && d_nrm && d_ref && d_mask && d_front && d_nb && d_adj && d_keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wsup_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, cell_size, adj_px, min_support, min_neigh, d_front, d_nb,
+                    d_adj, d_keep, s);
+        return 0;
+    });
+}
+
+// the host-pointer call's arrays inside q_buf, in 8-byte words: c, nrm (3 n
+// each), mask (n words), then the int32 arrays ref, nb, adj (n each) and front
+// (cells), then keep
+struct WsupHost {
+    int64_t n, cells, words;
+    int64_t total() const { return n * (6 + words) + 3 * ((n + 1) / 2) + (cells + 1) / 2 + (n + 7) / 8; }
+    double* c(int64_t* b) const { return (double*)b; }
+    double* nrm(int64_t* b) const { return (double*)b + 3 * n; }
+    uint64_t* mask(int64_t* b) const { return (uint64_t*)b + 6 * n; }
+    int32_t* ref(int64_t* b) const { return (int32_t*)(b + n * (6 + words)); }
+    int32_t* nb(int64_t* b) const { return (int32_t*)(b + n * (6 + words) + (n + 1) / 2); }
+    int32_t* adj(int64_t* b) const { return (int32_t*)(b + n * (6 + words) + 2 * ((n + 1) / 2)); }
+    int32_t* front(int64_t* b) const { return (int32_t*)(b + n * (6 + words) + 3 * ((n + 1) / 2)); }
+    uint8_t* keep(int64_t* b) const { return (uint8_t*)(b + n * (6 + words) + 3 * ((n + 1) / 2) + (cells + 1) / 2); }
+};
+
+int mvs_wfilt_support(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                      const uint64_t* mask, int cell_size, double adj_px, double min_support, int min_neigh,
+                      const int32_t* front, int32_t* nb, int32_t* adj, uint8_t* keep) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wsup_check(ctx, n, cell_size, adj_px, min_support, min_neigh,
+                            c && nrm && ref && mask && front && nb && adj && keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const WsupHost h{n, (int64_t)ctx->V * (ctx->H / cell_size) * (ctx->W / cell_size), (ctx->V + 63) / 64};
+        for (int64_t k = 0; k < h.cells; ++k)
+            if (front[k] < -1 || front[k] >= n)
+                throw Fail{MVS_E_ARG, "mvs_wfilt_support: front entry outside -1..n-1"};
+        ctx->q_buf.ensure(h.total());
+        int64_t* b = ctx->q_buf.p;
+        HIPCHK(hipMemcpyAsync(h.c(b), c, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.nrm(b), nrm, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.mask(b), mask, n * h.words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(h.ref(b), ref, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (h.cells) HIPCHK(hipMemcpyAsync(h.front(b), front, h.cells * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        wsup_launch(ctx, n, h.c(b), h.nrm(b), h.ref(b), h.mask(b), cell_size, adj_px, min_support, min_neigh,
+                    h.front(b), h.nb(b), h.adj(b), h.keep(b), s);
+        HIPCHK(hipMemcpyAsync(nb, h.nb(b), n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(adj, h.adj(b), n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(keep, h.keep(b), n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
 int64_t mvs_exact_hits(mvs_ctx* ctx) {
     if (!ctx) return MVS_E_ARG;
     int32_t h = 0;

@@ -21,6 +21,12 @@
 //   counted lane adds w(p) onto conf[f] (64-bit vector atomic add); the wave's
 //   sum of w(f) goes onto conf[p] by one more.  Integer sums: order-free.
 // k_wfilt_decide: one thread per patch, after the conflict kernel.
+// k_wfilt_support (mvs_wfilt_support): the same layout, a runtime loop over the
+//   groups of 64 views.  A lane places the patch in its view, gathers the front
+//   patches of the eight cells around that cell and their centres and normals,
+//   and counts the neighbours (N) and the adjacent ones (A); the wave's sums
+//   come from shuffles and one lane writes nb, adj and keep.  No atomics, no
+//   LDS, no barrier.
 // Binary64 in the library's operation order, compiled with -ffp-contract=off.
 #include <algorithm>
 
@@ -30,8 +36,8 @@ namespace {
 
 constexpr uint64_t kInfBits = 0x7ff0000000000000ull;
 
-// the cell of the patch centre in view v and its depth there; false when the patch is not placed
-DEV bool place(const SceneDev& sc, int v, const double* c, int cs, int nci, int ncj, int64_t* cell, double* depth) {
+// the cell (i, j) of the patch centre in view v and its depth there; false when the patch is not placed
+DEV bool place_ij(const SceneDev& sc, int v, const double* c, int cs, int nci, int ncj, int* i, int* j, double* depth) {
     const CamDev& cv = sc.cams[v];
     double px, py;
     project(cv, c, px, py);
@@ -40,8 +46,17 @@ DEV bool place(const SceneDev& sc, int v, const double* c, int cs, int nci, int 
     if (!(z > 0.0 && px >= 0.0 && px < (double)sc.W && py >= 0.0 && py < (double)sc.H)) return false;
     const int ci = (int)px / cs, cj = (int)py / cs;
     if (ci >= nci || cj >= ncj) return false;
-    *cell = ((int64_t)v * ncj + cj) * nci + ci;
+    *i = ci;
+    *j = cj;
     *depth = z;
+    return true;
+}
+
+// the same with the cell as its index in the (V, ncj, nci) grids
+DEV bool place(const SceneDev& sc, int v, const double* c, int cs, int nci, int ncj, int64_t* cell, double* depth) {
+    int ci, cj;
+    if (!place_ij(sc, v, c, cs, nci, ncj, &ci, &cj, depth)) return false;
+    *cell = ((int64_t)v * ncj + cj) * nci + ci;
     return true;
 }
 
@@ -190,6 +205,85 @@ __global__ __launch_bounds__(256) void k_wfilt_decide(int V, const WfiltArgs a) 
     a.keep[p] = seen >= a.min_views && (int64_t)tv * weight(a.avg[p]) >= a.conf[p];
 }
 
+DEV int wave_sum32(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+
+// The neighbour-support test: a lane places the patch in its view and walks the
+// eight cells around that cell.  Every neighbour cell whose front patch q is
+// another patch is one incidence (N); it supports p (A) when p and q are
+// adjacent in that view.  No state survives a group of 64 views but the two
+// counts, so the groups are a runtime loop.  The gathers are latency-bound:
+// eight waves per SIMD (at most 64 VGPRs) is asked for, the family's occupancy.
+__global__ __launch_bounds__(256, 8) void k_wfilt_support(const SceneDev sc, const WsupArgs a) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + wave;
+    if (p >= a.n) return;
+    const int V = sc.V, words = (V + 63) >> 6;
+    const int cs = a.cell_size, nci = sc.W / cs, ncj = sc.H / cs;
+    const int R = __builtin_amdgcn_readfirstlane(a.ref[p]);
+    if (R < 0 || R >= V) {   // a dead row: no neighbour, not kept
+        if (lane == 0) {
+            a.nb[p] = 0;
+            a.adj[p] = 0;
+            a.keep[p] = 0;
+        }
+        return;
+    }
+    const double c[3] = {a.c[3 * p], a.c[3 * p + 1], a.c[3 * p + 2]};
+    const double n[3] = {a.nrm[3 * p], a.nrm[3 * p + 1], a.nrm[3 * p + 2]};
+    int N = 0, A = 0;
+    for (int g0 = 0; g0 < V; g0 += 64) {
+        const int v = g0 + lane;
+        const uint64_t word = a.mask[p * words + (g0 >> 6)];
+        if (v >= V || !(v == R || ((word >> lane) & 1))) continue;
+        int ci, cj;
+        double z;
+        if (!place_ij(sc, v, c, cs, nci, ncj, &ci, &cj, &z)) continue;
+        const double rho = (a.adj_px * z) / ((sc.cams[v].fx + sc.cams[v].fy) / 2);
+        const double lim = 2.0 * rho;
+        // a row of the neighbourhood at a time: its three front entries first (independent
+        // 4-byte gathers), then the rows they name.  A skipped neighbour reads p's own row
+        // (in cache), so the loads need no branch and overlap.
+#pragma unroll 1
+        for (int dj = -1; dj <= 1; ++dj) {
+            const int j = cj + dj;
+            if (j < 0 || j >= ncj) continue;
+            const int32_t* const row = a.front + ((int64_t)v * ncj + j) * nci;
+            int q[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int i = ci + k - 1;
+                int f = -1;
+                if (i >= 0 && i < nci && !(dj == 0 && k == 1)) f = row[i];
+                if (f < -1 || f >= a.n || f == p) f = -1;   // reads nothing; p itself is no neighbour
+                q[k] = f;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int64_t r = q[k] < 0 ? p : (int64_t)q[k];
+                const double* const cf = a.c + 3 * r;
+                const double* const nf = a.nrm + 3 * r;
+                const double d[3] = {c[0] - cf[0], c[1] - cf[1], c[2] - cf[2]};
+                const double dp = d[0] * n[0] + d[1] * n[1] + d[2] * n[2];
+                const double df = d[0] * nf[0] + d[1] * nf[1] + d[2] * nf[2];
+                N += q[k] >= 0;
+                A += q[k] >= 0 && fabs(dp) + fabs(df) < lim;   // nan: not adjacent
+            }
+        }
+    }
+    N = wave_sum32(N);
+    A = wave_sum32(A);
+    if (lane == 0) {
+        a.nb[p] = N;
+        a.adj[p] = A;
+        a.keep[p] = N >= a.min_neigh && (double)A >= a.min_support * (double)N;
+    }
+}
+
 bool launched() { return hipGetLastError() == hipSuccess; }
 
 }  // namespace
@@ -222,6 +316,12 @@ extern "C" int mvs_launch_wfilt_test(const SceneDev* sc, const WfiltArgs* a, hip
     }
     if (!launched()) return -1;
     hipLaunchKernelGGL(k_wfilt_decide, dim3((unsigned)((a->n + 255) / 256)), dim3(256), 0, s, sc->V, *a);
+    return launched() ? 0 : -1;
+}
+
+extern "C" int mvs_launch_wfilt_support(const SceneDev* sc, const WsupArgs* a, hipStream_t s) {
+    if (a->n <= 0) return 0;
+    hipLaunchKernelGGL(k_wfilt_support, dim3((unsigned)((a->n + 3) / 4)), dim3(256), 0, s, *sc, *a);
     return launched() ? 0 : -1;
 }
 static_assert(MVS_MAX_VIEWS == 256, "k_wfilt_conflict holds at most four front patches per lane");

@@ -169,6 +169,21 @@ struct WfiltArgs {
     int64_t* conf;          // n
     uint8_t* keep;          // n
 };
+// The neighbour-support test (mvs_filter_warp.hip; device pointers): the rows
+// and the front grid as above, read only.
+struct WsupArgs {
+    int64_t n;
+    const double* c;        // n*3
+    const double* nrm;      // n*3
+    const int32_t* ref;     // n; outside 0..V-1 = a dead row
+    const uint64_t* mask;   // n*words
+    int cell_size, min_neigh;
+    double adj_px, min_support;
+    const int32_t* front;   // V*ncj*nci
+    int32_t* nb;            // n: N(p)
+    int32_t* adj;           // n: A(p)
+    uint8_t* keep;          // n
+};
 
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
@@ -364,9 +379,10 @@ int mvs_launch_wexp_claim(const ClaimArgs* a, hipStream_t s);
 int mvs_launch_wexp_mark(const SceneDev* sc, const MarkArgs* a, hipStream_t s);
 // the visibility-consistency filter (mvs_filter_warp.hip): front = k_wfilt_fill,
 // k_wfilt_front depth pass and index pass; test = conf to zero, k_wfilt_conflict,
-// k_wfilt_decide
+// k_wfilt_decide; support = k_wfilt_support
 int mvs_launch_wfilt_front(const SceneDev* sc, const WfiltArgs* a, hipStream_t s);
 int mvs_launch_wfilt_test(const SceneDev* sc, const WfiltArgs* a, hipStream_t s);
+int mvs_launch_wfilt_support(const SceneDev* sc, const WsupArgs* a, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

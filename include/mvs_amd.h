@@ -382,8 +382,9 @@ int mvs_wexp_mark_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const ui
  * Neither call keeps context state: they may run on any stream beside any other
  * call, and interleave freely with every other call.  Results are deterministic.
  * The host-pointer variants mvs_wfilt_front and mvs_wfilt_test are synchronous,
- * on the context's stream and a buffer of their own; mvs_wfilt_test returns
- * MVS_E_ARG for a front entry outside -1..n-1.
+ * on the context's stream and the staging buffer that every host-pointer call
+ * of the context shares (none keeps anything there past its return);
+ * mvs_wfilt_test returns MVS_E_ARG for a front entry outside -1..n-1.
  * MVS_E_ARG (message in mvs_last_error) for a scalar out of range (cell_size,
  * adj_px negative, nan or inf, min_views < 0), a NULL pointer, n < 0 or
  * n >= 2^31. */
@@ -432,8 +433,8 @@ int mvs_wfilt_test(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, 
  * shuffles.  No atomics, no scratch and no context state: it may run on any
  * stream beside any other call.  Results are deterministic.
  * The host-pointer variant mvs_wfilt_support is synchronous, on the context's
- * stream and a buffer of its own, and returns MVS_E_ARG for a front entry
- * outside -1..n-1.
+ * stream and the host-pointer calls' shared staging buffer, and returns
+ * MVS_E_ARG for a front entry outside -1..n-1.
  * MVS_E_ARG (message in mvs_last_error) for a scalar out of range (cell_size,
  * adj_px negative, nan or inf, min_support nan or outside [0, 1], min_neigh <
  * 0), a NULL pointer, n < 0 or n >= 2^31. */

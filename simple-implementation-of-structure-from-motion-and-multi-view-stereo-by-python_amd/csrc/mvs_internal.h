@@ -1,5 +1,5 @@
 // Internal declarations shared by the HIP units (mvs_*.hip, sfm_kernels.hip)
-// and the host engine (mvs_engine.cpp).  Not part of the
+// and the host sources (mvs_*.cpp, through mvs_host.h).  Not part of the
 // public C-ABI (include/mvs_amd.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,7 +10,7 @@
 
 // Per-view camera constants, laid out for wave-uniform (scalar) loads.
 // All values are computed on the host in the reference's operation order
-// (see mvs_engine.cpp: build_cameras).
+// (see mvs_context.cpp: build_cameras).
 struct CamDev {
     double Rp[9];   // Rodrigues round-trip of R (what cv2.projectPoints uses, utils.py:242-243)
     double t[3];

@@ -1,0 +1,644 @@
+// The warped family's C-ABI of libmvs_amd.so: the plane-warped photo test,
+// the refinement level and its view lists, the warped expansion's primitives,
+// the visibility-consistency filter and the neighbour-support test.
+#include <cmath>
+
+#include "mvs_host.h"
+
+// The checks every family repeats, each under the family's own name `who`
+// (0, or the error's code with the message recorded).
+static int bad_arg(mvs_ctx* ctx, const char* who, const std::string& what) {
+    return set_err(ctx, Fail{MVS_E_ARG, std::string(who) + ": " + what});
+}
+static int need_nonneg(mvs_ctx* ctx, const char* who, const char* name, int64_t v) {
+    return v < 0 ? bad_arg(ctx, who, std::string(name) + " < 0") : 0;
+}
+// a row count: 2^31 itself passes here (the filter family refuses it, in wfilt_check)
+static int need_count(mvs_ctx* ctx, const char* who, const char* name, int64_t n) {
+    if (int rc = need_nonneg(ctx, who, name, n)) return rc;
+    return n > ((int64_t)1 << 31) ? bad_arg(ctx, who, std::string(name) + " above 2^31") : 0;
+}
+static int need_wid(mvs_ctx* ctx, const char* who, int wid) {
+    return wid < 1 || wid > MVS_MAX_WID ? bad_arg(ctx, who, "wid must be in 1..5") : 0;
+}
+static int need_min_cos(mvs_ctx* ctx, const char* who, double min_cos) {
+    return !(min_cos >= 0.0 && min_cos < 1.0) ? bad_arg(ctx, who, "min_cos must be in [0, 1)") : 0;
+}
+static int need_cell_size(mvs_ctx* ctx, const char* who, int cell_size) {
+    return cell_size < 1 || cell_size > 16 ? bad_arg(ctx, who, "cell_size must be in 1..16") : 0;
+}
+
+extern "C" {
+
+// argument checks shared by the two entry points of the plane-warped test
+static int warp_check(mvs_ctx* ctx, int64_t n, bool ptrs_ok, int wid, double min_cos) {
+    if (int rc = need_count(ctx, "mvs_score_warped", "n", n)) return rc;
+    if (int rc = need_wid(ctx, "mvs_score_warped", wid)) return rc;
+    if (int rc = need_min_cos(ctx, "mvs_score_warped", min_cos)) return rc;
+    if (n > 0 && !ptrs_ok) return set_err(ctx, Fail{MVS_E_ARG, "mvs_score_warped: null pointer (only avg and ncc may be NULL)"});
+    return 0;
+}
+
+static void warp_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                        int wid, double min_ncc, double min_cos, double* d_xy, uint64_t* d_mask, int32_t* d_count,
+                        double* d_avg, double* d_ncc, hipStream_t s) {
+    WarpArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.min_ncc = min_ncc;
+    a.min_cos = min_cos;
+    a.xy = d_xy;
+    a.mask = d_mask;
+    a.count = d_count;
+    a.avg = d_avg;
+    a.ncc = d_ncc;
+    if (mvs_launch_score_warp(&ctx->sc, &a, wid, s) != 0) throw Fail{MVS_E_HIP, "score_warp launch failed"};
+}
+
+int mvs_score_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                            int wid, double min_ncc, double min_cos, double* d_xy, uint64_t* d_mask,
+                            int32_t* d_count, double* d_avg, double* d_ncc, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = warp_check(ctx, n, d_c && d_nrm && d_ref && d_xy && d_mask && d_count, wid, min_cos)) return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        warp_launch(ctx, n, d_c, d_nrm, d_ref, wid, min_ncc, min_cos, d_xy, d_mask, d_count, d_avg, d_ncc, s);
+        return 0;
+    });
+}
+
+int mvs_score_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref, int wid,
+                     double min_ncc, double min_cos, double* xy, uint64_t* mask, int32_t* count, double* avg,
+                     double* ncc) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = warp_check(ctx, n, c && nrm && ref && xy && mask && count, wid, min_cos)) return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        for (int64_t i = 0; i < n; ++i)
+            if (ref[i] < 0 || ref[i] >= ctx->V) throw Fail{MVS_E_ARG, "mvs_score_warped: ref view out of range"};
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_nrm = st.in(nrm, n * 3);
+        const auto d_ref = st.in(ref, n);
+        const auto d_xy = st.out(xy, n * 2);
+        const auto d_mask = st.out(mask, n * ctx->words());
+        const auto d_count = st.out(count, n);
+        const auto d_avg = st.out(avg, n);
+        const auto d_ncc = st.out(ncc, n * ctx->V);
+        st.upload();
+        warp_launch(ctx, n, d_c, d_nrm, d_ref, wid, min_ncc, min_cos, d_xy, d_mask, d_count, d_avg, d_ncc, s);
+        st.finish();
+        return 0;
+    });
+}
+
+// argument checks shared by the two entry points of the refinement level
+static int refine_check(mvs_ctx* ctx, int64_t n, bool ptrs_ok, int tv, int wid, double min_cos, int kd, int ka,
+                        double astep, double step_scale) {
+    if (int rc = need_count(ctx, "mvs_refine_warped", "n", n)) return rc;
+    if (int rc = need_wid(ctx, "mvs_refine_warped", wid)) return rc;
+    if (int rc = need_min_cos(ctx, "mvs_refine_warped", min_cos)) return rc;
+    if (tv < 1 || tv > 32) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: tv must be in 1..32"});
+    if (kd < 0 || kd > 3) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: kd must be in 0..3"});
+    if (ka < 0 || ka > 2) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: ka must be in 0..2"});
+    if (!(step_scale > 0.0) || !std::isfinite(step_scale))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: step_scale must be > 0"});
+    if (!(astep >= 0.0) || !((double)ka * astep * step_scale <= 1.2))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: ka * astep * step_scale must be in [0, 1.2]"});
+    if (n > 0 && !ptrs_ok)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_warped: null pointer (only scores may be NULL)"});
+    return 0;
+}
+
+static void refine_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                          const int32_t* d_views, int tv, const double* d_dstep, int wid, double min_cos, int kd,
+                          int ka, double astep, double step_scale, double* d_c_out, double* d_nrm_out,
+                          int32_t* d_best, double* d_score_best, double* d_scores, hipStream_t s) {
+    RefineArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.views = d_views;
+    a.dstep = d_dstep;
+    a.tv = tv;
+    a.kd = kd;
+    a.ka = ka;
+    a.min_cos = min_cos;
+    a.step_scale = step_scale;
+    // the grid's tangents from the host's libm (what a caller's own tan() gives)
+    const double alpha = astep * step_scale;
+    for (int i = -ka; i <= ka; ++i) a.tans[i + ka] = std::tan((double)i * alpha);
+    a.c_out = d_c_out;
+    a.nrm_out = d_nrm_out;
+    a.best = d_best;
+    a.score_best = d_score_best;
+    a.scores = d_scores;
+    if (mvs_launch_refine_warp(&ctx->sc, &a, wid, s) != 0) throw Fail{MVS_E_HIP, "refine_warp launch failed"};
+}
+
+int mvs_refine_warped_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                             const int32_t* d_views, int tv, const double* d_dstep, int wid, double min_cos, int kd,
+                             int ka, double astep, double step_scale, double* d_c_out, double* d_nrm_out,
+                             int32_t* d_best, double* d_score_best, double* d_scores, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = refine_check(ctx, n, d_c && d_nrm && d_ref && d_views && d_dstep && d_c_out && d_nrm_out && d_best &&
+                                          d_score_best, tv, wid, min_cos, kd, ka, astep, step_scale))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        refine_launch(ctx, n, d_c, d_nrm, d_ref, d_views, tv, d_dstep, wid, min_cos, kd, ka, astep, step_scale,
+                      d_c_out, d_nrm_out, d_best, d_score_best, d_scores, s);
+        return 0;
+    });
+}
+
+int mvs_refine_warped(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                      const int32_t* views, int tv, const double* dstep, int wid, double min_cos, int kd, int ka,
+                      double astep, double step_scale, double* c_out, double* nrm_out, int32_t* best,
+                      double* score_best, double* scores) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = refine_check(ctx, n, c && nrm && ref && views && dstep && c_out && nrm_out && best && score_best,
+                              tv, wid, min_cos, kd, ka, astep, step_scale))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        const int V = ctx->V;
+        for (int64_t i = 0; i < n; ++i) {
+            if (ref[i] < 0 || ref[i] >= V) throw Fail{MVS_E_ARG, "mvs_refine_warped: ref view out of range"};
+            const int32_t* l = views + i * tv;
+            bool ended = false;
+            for (int j = 0; j < tv; ++j) {
+                if (l[j] < -1 || l[j] >= V) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view out of range"};
+                if (l[j] < 0) { ended = true; continue; }
+                if (ended) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view after a -1"};
+                if (l[j] == ref[i]) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view equal to ref"};
+                for (int k = 0; k < j; ++k)
+                    if (l[k] == l[j]) throw Fail{MVS_E_ARG, "mvs_refine_warped: list view repeated"};
+            }
+        }
+        hipStream_t s = ctx->stream;
+        const int A = 2 * ka + 1;
+        const int64_t H = (int64_t)(2 * kd + 1) * A * A;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_nrm = st.in(nrm, n * 3);
+        const auto d_dstep = st.in(dstep, n);
+        const auto d_ref = st.in(ref, n);
+        const auto d_views = st.in(views, n * tv);
+        const auto d_co = st.out(c_out, n * 3);
+        const auto d_no = st.out(nrm_out, n * 3);
+        const auto d_sb = st.out(score_best, n);
+        const auto d_best = st.out(best, n);
+        const auto d_scores = st.out(scores, n * H);
+        st.upload();
+        refine_launch(ctx, n, d_c, d_nrm, d_ref, d_views, tv, d_dstep, wid, min_cos, kd, ka, astep, step_scale, d_co,
+                      d_no, d_best, d_sb, d_scores, s);
+        st.finish();
+        return 0;
+    });
+}
+
+// argument checks shared by the two entry points of the list builder
+static int lists_check(mvs_ctx* ctx, int64_t n, int64_t rows, bool has_sel, bool ptrs_ok, double min_ncc,
+                       int max_views, double depth_px) {
+    if (int rc = need_nonneg(ctx, "mvs_refine_lists", "n", n)) return rc;
+    if (int rc = need_nonneg(ctx, "mvs_refine_lists", "rows", rows)) return rc;
+    if (n > ((int64_t)1 << 31) || rows > ((int64_t)1 << 31))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: n or rows above 2^31"});
+    if (max_views < 1 || max_views > 32)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: max_views must be in 1..32"});
+    if (std::isnan(min_ncc)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: min_ncc is nan"});
+    if (!std::isfinite(depth_px) || !(depth_px > 0.0))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: depth_px must be finite and > 0"});
+    if (!has_sel && n > rows) return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: n > rows without sel"});
+    if (n > 0 && !ptrs_ok)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_refine_lists: null pointer (only sel and dstep, and c and ref "
+                                            "without dstep, may be NULL)"});
+    return 0;
+}
+
+static void lists_launch(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* d_sel, const double* d_ncc,
+                         const double* d_c, const int32_t* d_ref, double min_ncc, int max_views, double depth_px,
+                         int32_t* d_views, double* d_dstep, hipStream_t s) {
+    ListArgs a{};
+    a.n = n;
+    a.rows = rows;
+    a.sel = d_sel;
+    a.ncc = d_ncc;
+    a.c = d_c;
+    a.ref = d_ref;
+    a.min_ncc = min_ncc;
+    a.depth_px = depth_px;
+    a.max_views = max_views;
+    a.views = d_views;
+    a.dstep = d_dstep;
+    if (mvs_launch_refine_lists(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "refine_lists launch failed"};
+}
+
+int mvs_refine_lists_device(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* d_sel, const double* d_ncc,
+                            const double* d_c, const int32_t* d_ref, double min_ncc, int max_views, double depth_px,
+                            int32_t* d_views, double* d_dstep, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = lists_check(ctx, n, rows, d_sel != nullptr, d_ncc && d_views && (!d_dstep || (d_c && d_ref)),
+                             min_ncc, max_views, depth_px))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        lists_launch(ctx, n, rows, d_sel, d_ncc, d_c, d_ref, min_ncc, max_views, depth_px, d_views, d_dstep, s);
+        return 0;
+    });
+}
+
+int mvs_refine_lists(mvs_ctx* ctx, int64_t n, int64_t rows, const int64_t* sel, const double* ncc, const double* c,
+                     const int32_t* ref, double min_ncc, int max_views, double depth_px, int32_t* views,
+                     double* dstep) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = lists_check(ctx, n, rows, sel != nullptr, ncc && views && (!dstep || (c && ref)), min_ncc,
+                             max_views, depth_px))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        const int V = ctx->V;
+        for (int64_t k = 0; sel && k < n; ++k)
+            if (sel[k] < 0 || sel[k] >= rows) throw Fail{MVS_E_ARG, "mvs_refine_lists: sel row out of range"};
+        for (int64_t k = 0; dstep && k < n; ++k) {
+            const int32_t r = ref[sel ? sel[k] : k];
+            if (r < 0 || r >= V) throw Fail{MVS_E_ARG, "mvs_refine_lists: ref view out of range"};
+        }
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_ncc = st.in(ncc, rows * V);
+        // c and ref are read for dstep alone: not copied without it
+        const auto d_c = st.in(dstep ? c : nullptr, rows * 3);
+        const auto d_ref = st.in(dstep ? ref : nullptr, rows);
+        const auto d_sel = st.in(sel, n);
+        const auto d_views = st.out(views, n * max_views);
+        const auto d_dstep = st.out(dstep, n);
+        st.upload();
+        lists_launch(ctx, n, rows, sel ? (int64_t*)d_sel : nullptr, d_ncc, d_c, d_ref, min_ncc, max_views, depth_px,
+                     d_views, d_dstep, s);
+        st.finish();
+        return 0;
+    });
+}
+
+// ---- the warped expansion's primitives (mvs_expand_warp.hip) ----
+
+int mvs_wexp_children_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                             const uint64_t* d_mask, int cell_size, const uint8_t* d_occ, double max_dist,
+                             int64_t cap, int32_t* d_job, double* d_cc, double* d_cn, int32_t* d_cref,
+                             int64_t* d_total, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = need_count(ctx, "mvs_wexp_children", "n", n)) return rc;
+    if (int rc = need_cell_size(ctx, "mvs_wexp_children", cell_size)) return rc;
+    if (!(max_dist > 0.0)) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: max_dist must be > 0"});
+    if (int rc = need_nonneg(ctx, "mvs_wexp_children", "cap", cap)) return rc;
+    if (n == 0) return MVS_OK;
+    if (!d_c || !d_nrm || !d_ref || !d_mask || !d_occ || !d_total ||
+        (cap > 0 && (!d_job || !d_cc || !d_cn || !d_cref)))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: null pointer (the outputs may be NULL when cap is 0)"});
+    if ((uintptr_t)d_job % 16) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_children: d_job must be 16-B aligned"});
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        ctx->wexp_order.acquire(s);
+        ctx->x_cnt.ensure(n);
+        ctx->x_offs.ensure(n + 1);
+        WexpArgs a{};
+        a.n = n;
+        a.c = d_c;
+        a.nrm = d_nrm;
+        a.ref = d_ref;
+        a.mask = d_mask;
+        a.cell_size = cell_size;
+        a.occ = d_occ;
+        a.max_dist = max_dist;
+        a.cap = cap;
+        a.cnt = ctx->x_cnt.p;
+        a.offs = ctx->x_offs.p;
+        a.job = (int4*)d_job;
+        a.cc = d_cc;
+        a.cn = d_cn;
+        a.cref = d_cref;
+        a.total = d_total;
+        if (mvs_launch_wexp_children(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wexp_children launch failed"};
+        ctx->wexp_order.release(s);
+        return 0;
+    });
+}
+
+static int claim_check(mvs_ctx* ctx, int64_t m, bool ptrs_ok, int nci, int ncj) {
+    if (int rc = need_count(ctx, "mvs_wexp_claim", "m", m)) return rc;
+    if (nci < 1 || ncj < 1 || nci > 65536 || ncj > 65536)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: nci and ncj must be in 1..65536"});
+    if (m > 0 && !ptrs_ok) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: null pointer"});
+    return 0;
+}
+
+// the claim on device pointers; the caller holds wexp_order
+static void claim_launch(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_accept,
+                         const double* d_score, int nci, int ncj, uint8_t* d_win, hipStream_t s) {
+    const size_t cells = (size_t)ctx->V * nci * ncj;
+    if (cells > ctx->x_key.n || cells > ctx->x_ticket.n) {
+        // new grids start clean; every call leaves them clean (hipFree of the old ones waits for their users)
+        ctx->x_key.alloc(cells);
+        ctx->x_ticket.alloc(cells);
+        HIPCHK(hipMemsetAsync(ctx->x_key.p, 0, ctx->x_key.n * sizeof(uint64_t), s));
+        HIPCHK(hipMemsetAsync(ctx->x_ticket.p, 0, ctx->x_ticket.n * sizeof(uint32_t), s));
+    }
+    ClaimArgs a{};
+    a.m = m;
+    a.job = (const int4*)d_job;
+    a.accept = d_accept;
+    a.score = d_score;
+    a.V = ctx->V;
+    a.nci = nci;
+    a.ncj = ncj;
+    a.key = ctx->x_key.p;
+    a.ticket = ctx->x_ticket.p;
+    a.win = d_win;
+    if (mvs_launch_wexp_claim(&a, s) != 0) throw Fail{MVS_E_HIP, "wexp_claim launch failed"};
+}
+
+int mvs_wexp_claim_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_accept,
+                          const double* d_score, int nci, int ncj, uint8_t* d_win, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = claim_check(ctx, m, d_job && d_accept && d_score && d_win, nci, ncj)) return rc;
+    if (m == 0) return MVS_OK;
+    if ((uintptr_t)d_job % 16) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_claim: d_job must be 16-B aligned"});
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        ctx->wexp_order.acquire(s);
+        claim_launch(ctx, m, d_job, d_accept, d_score, nci, ncj, d_win, s);
+        ctx->wexp_order.release(s);
+        return 0;
+    });
+}
+
+int mvs_wexp_claim(mvs_ctx* ctx, int64_t m, const int32_t* job, const uint8_t* accept, const double* score, int nci,
+                   int ncj, uint8_t* win) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = claim_check(ctx, m, job && accept && score && win, nci, ncj)) return rc;
+    if (m == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        for (int64_t k = 0; k < m; ++k) {
+            const int32_t* j = job + 4 * k;
+            if (j[1] < 0 || j[1] >= ctx->V || j[2] < 0 || j[2] >= nci || j[3] < 0 || j[3] >= ncj)
+                throw Fail{MVS_E_ARG, "mvs_wexp_claim: job (view, cell) outside the grid"};
+        }
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_job = st.in(job, 4 * m);
+        const auto d_accept = st.in(accept, m);
+        const auto d_score = st.in(score, m);
+        const auto d_win = st.out(win, m);
+        ctx->wexp_order.acquire(s);
+        st.upload();
+        claim_launch(ctx, m, d_job, d_accept, d_score, nci, ncj, d_win, s);
+        ctx->wexp_order.release(s);
+        st.finish();
+        return 0;
+    });
+}
+
+int mvs_wexp_mark_device(mvs_ctx* ctx, int64_t m, const int32_t* d_job, const uint8_t* d_win, const double* d_cc,
+                         const int32_t* d_cref, const uint64_t* d_mask, int cell_size, uint8_t* d_occ,
+                         void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = need_count(ctx, "mvs_wexp_mark", "m", m)) return rc;
+    if (int rc = need_cell_size(ctx, "mvs_wexp_mark", cell_size)) return rc;
+    if (m == 0) return MVS_OK;
+    if (!d_job || !d_win || !d_cc || !d_cref || !d_mask || !d_occ)
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: null pointer"});
+    if ((uintptr_t)d_job % 16) return set_err(ctx, Fail{MVS_E_ARG, "mvs_wexp_mark: d_job must be 16-B aligned"});
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        MarkArgs a{};
+        a.m = m;
+        a.job = (const int4*)d_job;
+        a.win = d_win;
+        a.cc = d_cc;
+        a.cref = d_cref;
+        a.mask = d_mask;
+        a.cell_size = cell_size;
+        a.occ = d_occ;
+        if (mvs_launch_wexp_mark(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wexp_mark launch failed"};
+        return 0;
+    });
+}
+
+// ---- the visibility-consistency filter (mvs_filter_warp.hip) ----
+
+static int wfilt_check(mvs_ctx* ctx, const char* who, int64_t n, int cell_size, double adj_px, int min_views,
+                       bool grids_ok, bool rows_ok) {
+    if (int rc = need_nonneg(ctx, who, "n", n)) return rc;
+    if (n >= ((int64_t)1 << 31)) return bad_arg(ctx, who, "n must be below 2^31");
+    if (int rc = need_cell_size(ctx, who, cell_size)) return rc;
+    if (!(adj_px >= 0.0 && adj_px < HUGE_VAL)) return bad_arg(ctx, who, "adj_px must be finite and >= 0");
+    if (int rc = need_nonneg(ctx, who, "min_views", min_views)) return rc;
+    if (!grids_ok || (n > 0 && !rows_ok)) return bad_arg(ctx, who, "null pointer");
+    return 0;
+}
+
+static void wfilt_front_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref,
+                               const uint64_t* d_mask, int cell_size, int32_t* d_front, double* d_zfront,
+                               hipStream_t s) {
+    WfiltArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.cell_size = cell_size;
+    a.front = d_front;
+    a.zfront = (uint64_t*)d_zfront;
+    if (mvs_launch_wfilt_front(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wfilt_front launch failed"};
+}
+
+static void wfilt_test_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                              const uint64_t* d_mask, const double* d_avg, int cell_size, double adj_px,
+                              int min_views, const int32_t* d_front, uint64_t* d_vis, int64_t* d_conf,
+                              uint8_t* d_keep, hipStream_t s) {
+    WfiltArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.avg = d_avg;
+    a.cell_size = cell_size;
+    a.adj_px = adj_px;
+    a.min_views = min_views;
+    a.front = const_cast<int32_t*>(d_front);   // read only by the test's kernels
+    a.vis = d_vis;
+    a.conf = d_conf;
+    a.keep = d_keep;
+    if (mvs_launch_wfilt_test(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wfilt_test launch failed"};
+}
+
+int mvs_wfilt_front_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref, const uint64_t* d_mask,
+                           int cell_size, int32_t* d_front, double* d_zfront, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_front", n, cell_size, 0.0, 0, d_front && d_zfront,
+                             d_c && d_ref && d_mask))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wfilt_front_launch(ctx, n, d_c, d_ref, d_mask, cell_size, d_front, d_zfront, s);
+        return 0;
+    });
+}
+
+int mvs_wfilt_test_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                          const uint64_t* d_mask, const double* d_avg, int cell_size, double adj_px, int min_views,
+                          const int32_t* d_front, uint64_t* d_vis, int64_t* d_conf, uint8_t* d_keep, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_test", n, cell_size, adj_px, min_views, true,
+                             d_c && d_nrm && d_ref && d_mask && d_avg && d_front && d_vis && d_conf && d_keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wfilt_test_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, d_avg, cell_size, adj_px, min_views, d_front, d_vis,
+                          d_conf, d_keep, s);
+        return 0;
+    });
+}
+
+int mvs_wfilt_front(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, const uint64_t* mask,
+                    int cell_size, int32_t* front, double* zfront) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_front", n, cell_size, 0.0, 0, front && zfront, c && ref && mask))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const int64_t cells = (int64_t)ctx->V * (ctx->H / cell_size) * (ctx->W / cell_size);
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_ref = st.in(ref, n);
+        const auto d_mask = st.in(mask, n * ctx->words());
+        const auto d_front = st.out(front, cells);
+        const auto d_zfront = st.out(zfront, cells);
+        st.upload();
+        wfilt_front_launch(ctx, n, d_c, d_ref, d_mask, cell_size, d_front, d_zfront, s);
+        st.finish();
+        return 0;
+    });
+}
+
+int mvs_wfilt_test(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                   const uint64_t* mask, const double* avg, int cell_size, double adj_px, int min_views,
+                   const int32_t* front, uint64_t* vis, int64_t* conf, uint8_t* keep) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_test", n, cell_size, adj_px, min_views, true,
+                             c && nrm && ref && mask && avg && front && vis && conf && keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const int64_t cells = (int64_t)ctx->V * (ctx->H / cell_size) * (ctx->W / cell_size);
+        for (int64_t k = 0; k < cells; ++k)
+            if (front[k] < -1 || front[k] >= n) throw Fail{MVS_E_ARG, "mvs_wfilt_test: front entry outside -1..n-1"};
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_nrm = st.in(nrm, n * 3);
+        const auto d_avg = st.in(avg, n);
+        const auto d_ref = st.in(ref, n);
+        const auto d_mask = st.in(mask, n * ctx->words());
+        const auto d_front = st.in(front, cells);
+        const auto d_vis = st.out(vis, n * ctx->words());
+        const auto d_conf = st.out(conf, n);
+        const auto d_keep = st.out(keep, n);
+        st.upload();
+        wfilt_test_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, d_avg, cell_size, adj_px, min_views, d_front, d_vis,
+                          d_conf, d_keep, s);
+        st.finish();
+        return 0;
+    });
+}
+
+// ---- the neighbour-support test (k_wfilt_support) ----
+
+static int wsup_check(mvs_ctx* ctx, int64_t n, int cell_size, double adj_px, double min_support, int min_neigh,
+                      bool rows_ok) {
+    if (int rc = wfilt_check(ctx, "mvs_wfilt_support", n, cell_size, adj_px, 0, true, rows_ok)) return rc;
+    if (!(min_support >= 0.0 && min_support <= 1.0))
+        return set_err(ctx, Fail{MVS_E_ARG, "mvs_wfilt_support: min_support must be in 0..1"});
+    if (int rc = need_nonneg(ctx, "mvs_wfilt_support", "min_neigh", min_neigh)) return rc;
+    return 0;
+}
+
+static void wsup_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                        const uint64_t* d_mask, int cell_size, double adj_px, double min_support, int min_neigh,
+                        const int32_t* d_front, int32_t* d_nb, int32_t* d_adj, uint8_t* d_keep, hipStream_t s) {
+    WsupArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.cell_size = cell_size;
+    a.min_neigh = min_neigh;
+    a.adj_px = adj_px;
+    a.min_support = min_support;
+    a.front = d_front;
+    a.nb = d_nb;
+    a.adj = d_adj;
+    a.keep = d_keep;
+    if (mvs_launch_wfilt_support(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wfilt_support launch failed"};
+}
+
+int mvs_wfilt_support_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                             const uint64_t* d_mask, int cell_size, double adj_px, double min_support,
+                             int min_neigh, const int32_t* d_front, int32_t* d_nb, int32_t* d_adj, uint8_t* d_keep,
+                             void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wsup_check(ctx, n, cell_size, adj_px, min_support, min_neigh,
+                            d_c && d_nrm && d_ref && d_mask && d_front && d_nb && d_adj && d_keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wsup_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, cell_size, adj_px, min_support, min_neigh, d_front, d_nb,
+                    d_adj, d_keep, s);
+        return 0;
+    });
+}
+
+int mvs_wfilt_support(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                      const uint64_t* mask, int cell_size, double adj_px, double min_support, int min_neigh,
+                      const int32_t* front, int32_t* nb, int32_t* adj, uint8_t* keep) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wsup_check(ctx, n, cell_size, adj_px, min_support, min_neigh,
+                            c && nrm && ref && mask && front && nb && adj && keep))
+        return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const int64_t cells = (int64_t)ctx->V * (ctx->H / cell_size) * (ctx->W / cell_size);
+        for (int64_t k = 0; k < cells; ++k)
+            if (front[k] < -1 || front[k] >= n)
+                throw Fail{MVS_E_ARG, "mvs_wfilt_support: front entry outside -1..n-1"};
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_nrm = st.in(nrm, n * 3);
+        const auto d_mask = st.in(mask, n * ctx->words());
+        const auto d_ref = st.in(ref, n);
+        const auto d_front = st.in(front, cells);
+        const auto d_nb = st.out(nb, n);
+        const auto d_adj = st.out(adj, n);
+        const auto d_keep = st.out(keep, n);
+        st.upload();
+        wsup_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, cell_size, adj_px, min_support, min_neigh, d_front, d_nb,
+                    d_adj, d_keep, s);
+        st.finish();
+        return 0;
+    });
+}
+
+}  // extern "C"

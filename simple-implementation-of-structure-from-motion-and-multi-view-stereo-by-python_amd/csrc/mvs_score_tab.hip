@@ -164,7 +164,8 @@ __global__ __launch_bounds__(256) void k_moments(const SceneDev sc, const Moment
 //      g_write below) between the units of the round before;
 //   2. wave w takes the item's M-blocks [w nblk / 8, (w+1) nblk / 8) and sorts
 //      its own candidates by row pair (ballots, in its own part of the list:
-//      no workgroup barrier), so that a unit's windows span few K-steps;
+//      no workgroup barrier), so that a unit's windows span few K-steps --
+//      WID + 1 to WID + 4, each with a K pass of exactly its length;
 //   3. units of two M-blocks of 16 candidates: C[m][v] = sum over the window
 //      of s_R s_v by v_mfma_i32_16x16x64_i8 (A = the reference window masked
 //      to candidate m's window, B = view v's region), exact; meanwhile S_b,
@@ -669,17 +670,19 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
                 for (int h = 0; h < NH; ++h)
 #pragma unroll
                     for (int nb = 0; nb < NBLK; ++nb) C[h][nb] = (v4i){0, 0, 0, 0};
-                // NST K-steps from sb; steps below sd are done (their A rows read
-                // zeros); steps [SAFE_LO, SAFE_HI] hold window rows of every
-                // candidate of the unit (no row test there)
-                auto kpass = [&](auto nstc, auto safe_lo_c, auto safe_hi_c, int sb, int sd) {
+                // NST K-steps from sb, one pass per span: the unit's candidates
+                // lie in the row pairs sb .. sb + NST - KSK, so the steps
+                // [SAFE_LO, SAFE_HI] = [NST - KSK + 1, KSK - 2] from sb hold a
+                // window row of every one of them, in both row parities (no
+                // row test there)
+                auto kpass = [&](auto nstc, int sb) {
                     constexpr int NST = decltype(nstc)::value;
-                    constexpr int SAFE_LO = decltype(safe_lo_c)::value, SAFE_HI = decltype(safe_hi_c)::value;
+                    constexpr int SAFE_LO = NST - KSK + 1, SAFE_HI = KSK - 2;
                     uint32_t rbp[NH];
                     int aoff[NH];
 #pragma unroll
                     for (int h = 0; h < NH; ++h) {
-                        rbp[h] = (rb[h] & ~((1u << (2 * sd)) - 1u)) >> (2 * sb);
+                        rbp[h] = rb[h] >> (2 * sb);
                         aoff[h] = Rv[h] * VS + lofs + 64 * sb;
                     }
                     const uint8_t* bptr[NBLK];
@@ -715,18 +718,14 @@ __global__ __launch_bounds__(kTabThreads, kTabMinWaves) void k_score_tab(const S
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 };
-                using I = std::integral_constant<int, 0>;
-                if (span <= KSK) {
-                    kpass(std::integral_constant<int, KSK>{}, std::integral_constant<int, 1>{},
-                          std::integral_constant<int, KSK - 2>{}, min(s_lo, KS - KSK), 0);
-                } else if (span == KSK + 1) {
-                    kpass(std::integral_constant<int, KSK + 1>{}, std::integral_constant<int, 2>{},
-                          std::integral_constant<int, KSK - 2>{}, min(s_lo, KS - KSK - 1), 0);
-                } else {
-                    for (int sd = s_lo; sd <= s_hi; sd += KSK)
-                        kpass(std::integral_constant<int, KSK>{}, std::integral_constant<int, KSK>{}, I{},
-                              min(sd, KS - KSK), sd);
-                }
+                // a span is KSK (one row pair) to KS = KSK + 3 (all four): a
+                // pass of exactly that many steps (the last one is the whole
+                // region, whatever the span)
+                static_assert(KS == KSK + 3, "four row pairs per tile");
+                if (span <= KSK) kpass(std::integral_constant<int, KSK>{}, min(s_lo, KS - KSK));
+                else if (span == KSK + 1) kpass(std::integral_constant<int, KSK + 1>{}, min(s_lo, KS - KSK - 1));
+                else if (span == KSK + 2) kpass(std::integral_constant<int, KSK + 2>{}, min(s_lo, KS - KSK - 2));
+                else kpass(std::integral_constant<int, KS>{}, 0);
                 TSTAMP(tk1);
                 TSTAMP_ADD(5, tk1 - tk0);
                 // the first candidate step's table values (issued after the K-loop:

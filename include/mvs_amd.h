@@ -445,6 +445,84 @@ int mvs_wfilt_support_device(mvs_ctx* ctx, int64_t n, const double* d_c, const d
 int mvs_wfilt_support(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
                       const uint64_t* mask, int cell_size, double adj_px, double min_support, int min_neigh,
                       const int32_t* front, int32_t* nb, int32_t* adj, uint8_t* keep);
+/* ---- Seeds of the warped pipeline from image features ----
+ * (no reference counterpart: the reference seeds from SfM tracks,
+ * MVS2.py:196-262).  PMVS's match step: every feature of a view is paired with
+ * the features of a neighbour view that lie along its epipolar line, and every
+ * such pair is triangulated into an oriented seed candidate; the photo test
+ * (mvs_score_warped) then tells the right candidates from the wrong ones and
+ * round 0 of MvsContext.expand_warped keeps the best per (view, cell).  The chain
+ * is MvsContext.seed_warped.  Cameras (Rp, t, fx fy cx cy, O_v = -Rp_v^T t_v)
+ * are mvs_score_warped's; "projection" is mvs_score's, (x, y, depth); integer
+ * coordinates are pixel centres; everything is binary64, unfused, products and
+ * sums taken left to right.
+ *
+ * Inputs: the features of all views in one device array d_feat (F x 2 int32,
+ * [col, row], mvs_harris_points' layout); feat_off (host, int64[V + 1],
+ * feat_off[0] = 0, not decreasing, F = feat_off[V] < 2^31): the features of view
+ * v are the rows feat_off[v] .. feat_off[v + 1] - 1; pairs (host, np x 2 int32):
+ * ordered view pairs (r, v), r != v, both in 0..V-1 (a pair may repeat); epi_px
+ * finite and > 0, min_sin2 in [0, 1), cap >= 0.
+ * For pair k = (r, v), feature a of r at pixel q_a and feature b of v at q_b (a
+ * and b local to their views):
+ *   1. d_a = Rp_r^T ((q_a.x-cx_r)/fx_r, (q_a.y-cy_r)/fy_r, 1), d_b likewise in v,
+ *      w = O_r - O_v.
+ *   2. A = d_a.d_a, B = d_a.d_b, C = d_b.d_b, D = d_a.w, E = d_b.w, den = A C - B B.
+ *      Skipped unless den > min_sin2 (A C): parallel rays and nan.
+ *   3. s = (B E - C D) / den, u = (A E - B D) / den, the parameters of the two
+ *      rays' closest points.  Skipped unless both are finite and > 0.
+ *   4. X = O_r + s d_a: on a's ray, so the seed projects onto its own feature in r.
+ *   5. (x, y, z) = projection of X into v.  Skipped unless z > 0 and err =
+ *      (x - q_b.x)^2 + (y - q_b.y)^2 <= epi_px^2 (one binary64 product).
+ *   6. The candidate: centre X, normal (O_r - X) / |O_r - X| (one sqrt, three
+ *      divides), reference view r, cand row (k, a, b, v), err.
+ * d_total[0] = the number of candidates (it may exceed cap).  They are compacted
+ * in the order (pair k, then a, then b) into d_c, d_nrm (cap*3), d_ref (cap),
+ * d_cand (cap*4 int32) and d_err (cap); only the first cap are written (cap = 0
+ * counts only: the five arrays may then be NULL).  The order comes from a count
+ * pass, a scan and an emit pass that repeats the count pass's arithmetic
+ * (k_wseed_pairs, k_wseed_scan), never from atomics: two runs are bit-identical.
+ * np = 0 or F = 0 returns MVS_OK, launches nothing and touches no context state
+ * (d_total is then not written).  MVS_E_ARG (message in mvs_last_error) for
+ * r = v, a view out of range, a feat_off that decreases or does not start at 0,
+ * a scalar out of range, np < 0, a NULL required pointer, and pairs whose
+ * reference views' features sum to 2^31 or more.
+ * The call uses none of the scorers' scratch or counter sets and may be
+ * interleaved freely with every other call; its per-row counts and offsets are
+ * the expansion's scratch, and calls on different streams are ordered on it.
+ * The host arrays are read before the call returns.  Stream-ordered (NULL = the
+ * context's stream). */
+int mvs_wseed_match_device(mvs_ctx* ctx, const int32_t* d_feat, const int64_t* feat_off, int64_t np,
+                           const int32_t* pairs, double epi_px, double min_sin2, int64_t cap, double* d_c,
+                           double* d_nrm, int32_t* d_ref, int32_t* d_cand, double* d_err, int64_t* d_total,
+                           void* stream);
+/* Same on host pointers; synchronous, on the context's stream and the
+ * host-pointer calls' shared staging buffer. */
+int mvs_wseed_match(mvs_ctx* ctx, const int32_t* feat, const int64_t* feat_off, int64_t np,
+                    const int32_t* pairs, double epi_px, double min_sin2, int64_t cap, double* c, double* nrm,
+                    int32_t* ref, int32_t* cand, double* err, int64_t* total);
+/* The colour of n patches from the context's resident RGB images (k_wpatch_color:
+ * one wave per patch, lane = view in groups of 64).  For patch p (centre
+ * c[3p..], reference view ref[p], mask[p*words..]) and every view v of {ref_p} U
+ * {v : mask bit v} inside 0..V-1 (a ref outside 0..V-1 names no view):
+ *   1. (x, y, depth) = projection of c_p into v (mvs_score's);
+ *   2. v counts when depth > 0, 0 <= x <= W-1 and 0 <= y <= H-1;
+ *   3. per channel, S = the bilinear sample at (x, y) in mvs_score_warped's
+ *      difference form (step 5 there) on the channel's bytes 0..255, unfused:
+ *      top = g00 + ax (g01 - g00), bot = g10 + ax (g11 - g10), S = top + ay (bot - top);
+ *   4. K = (int64) floor(S 256 + 0.5);
+ *   5. color[3p + ch] = (double)(sum of K over the m counted views) / (double)(256 m):
+ *      integer sums, so the result does not depend on the reduction order;
+ *   6. m = 0 gives 0, 0, 0.
+ * color (n*3 binary64), nviews (n int32) = m.  n = 0 returns MVS_OK and launches
+ * nothing; MVS_E_ARG for n < 0, n >= 2^31 or a NULL pointer.  No scratch, no
+ * atomics and no context state: it may run on any stream beside any other
+ * call.  Stream-ordered (NULL = the context's stream). */
+int mvs_wpatch_color_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref,
+                            const uint64_t* d_mask, double* d_color, int32_t* d_nviews, void* stream);
+/* Same on host pointers; synchronous. */
+int mvs_wpatch_color(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, const uint64_t* mask,
+                     double* color, int32_t* nviews);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

@@ -15,6 +15,12 @@ reference's Harris/NCC features (HarrisFeatures.py) matched on the GPU in
 place of OpenCV's ORB + FLANN + RANSAC (absent from this image); with -seeds
 FILE.npz (track_off, obs_view, obs_xy, the format tests/golden/make_seeds.py
 and -save_tracks write) the tracks are read instead.
+
+--warped runs the warped pipeline instead (MVS2.DensePointsWarped: seeds from
+Harris features along epipolar lines, expand -> filter) and writes
+warped_patches.ply, an oriented point cloud; it needs neither SfM nor -seeds:
+
+    python main.py -img_p data/dinoRing -par_p data/dinoRing/dinoR_par.txt -t png --warped
 """
 import importlib
 import os
@@ -39,6 +45,13 @@ def main(args, threshold=0.01, MIN_REPROJECTION_ERROR=0.3):
         if not dist.is_initialized():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     imgs = mvs.read_imgs(args)
+    if getattr(args, "warped", False):
+        # the warped pipeline in place of SfM and the stage: seeds from Harris
+        # features along epipolar lines, expand -> filter, warped_patches.ply
+        # with normals (MVS2.DensePointsWarped); single process
+        mvs.DensePointsWarped(imgs, args, rounds=args.warped_rounds, iterations=args.warped_iterations,
+                              epi_px=args.epi_px, expand={"cell_size": args.cell_size})
+        return
     if getattr(args, "seeds", None):
         global_set = mvs.SeedSet.load(args.seeds)
     else:
@@ -78,6 +91,15 @@ if __name__ == "__main__":
                              "reference has the call commented out, MVS2.py:281)")
     parser.add_argument("-save_tracks", help="write the SfM tracks (npz) before the MVS stage",
                         dest="save_tracks", default=None)
+    parser.add_argument("--warped", dest="warped", action="store_true",
+                        help="run the warped pipeline (feature seeds, expand, filter) in place of SfM and "
+                             "the stage; writes warped_patches.ply with normals; needs no -seeds")
+    parser.add_argument("-warped_rounds", dest="warped_rounds", default=4, type=int,
+                        help="--warped: expansion rounds from the seeds")
+    parser.add_argument("-warped_iterations", dest="warped_iterations", default=3, type=int,
+                        help="--warped: filter / resumption iterations")
+    parser.add_argument("-epi_px", dest="epi_px", default=1.5, type=float,
+                        help="--warped: the seed matcher's distance from the epipolar line, pixels")
     args = parser.parse_args()
     try:
         main(args)

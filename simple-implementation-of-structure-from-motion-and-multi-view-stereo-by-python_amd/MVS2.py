@@ -16,7 +16,7 @@ import zlib
 import numpy as np
 
 from . import _lib
-from .utils import export2ply, pars_to_arrays, read_pars, tracks_to_arrays
+from .utils import export2ply, export2ply_oriented, pars_to_arrays, read_pars, tracks_to_arrays
 
 last_stats = {}
 _ctx_cache = {}
@@ -154,6 +154,55 @@ def reconstruct_patches_warped(ctx, centroids, normals, ref_views, **kw):
     counterpart; see MvsContext.reconstruct_warped, which takes the keywords):
     the filtered patch set grown from the seed patches, and the loop's history."""
     return ctx.reconstruct_warped(centroids, normals, ref_views, **kw)
+
+
+def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1e-4, neighbours=4, min_axis_cos=0.5,
+                      feats=None, pairs=None, path="warped_patches", device=None, **kw):
+    """An oriented, coloured point cloud from calibrated images alone (no
+    reference counterpart; PMVS's match -> expand -> filter on the warped
+    pipeline, without SfM tracks):
+
+      1. read_pars(args) and the scene context;
+      2. MvsContext.seed_warped: Harris features of every view matched along the
+         epipolar lines of their neighbour views (wseed_pairs(neighbours,
+         min_axis_cos), epi_px, min_sin2) into oriented seed candidates
+         (feats, pairs: the caller's own features and view pairs instead);
+      3. MvsContext.reconstruct_warped from them: `rounds` rounds of
+         expand_warped (its round 0 keeps the best-scoring candidate per
+         (reference view, cell)), then `iterations` of filter and resumption;
+         the remaining keywords (resume_rounds, expand, filter) are its own;
+      4. MvsContext.wpatch_color of the final set;
+      5. export2ply_oriented -> path + '.ply' (points, normals, colours);
+      6. one line of counts.
+
+    Returns a dict: points, normals, colors (n,3), nviews, patches (the final
+    set as reconstruct_warped returns it) and counts (features, pairs, tests,
+    candidates, winners0, patches per iteration); the counts are also left in
+    MVS2.last_stats."""
+    t0 = time.time()
+    par_K, par_r, par_t = read_pars(args)
+    ctx = scene_context(imgs, par_K, par_r, par_t, device)
+    expand = dict(kw.pop("expand", None) or {})
+    if pairs is None:
+        pairs = ctx.wseed_pairs(neighbours, min_axis_cos)
+    c, nrm, ref, cand, err = ctx.seed_warped(feats=feats, pairs=pairs, epi_px=epi_px, min_sin2=min_sin2,
+                                             wid=expand.get("wid", 5))
+    counts = {k: ctx.last_seed[k] for k in ("features", "pairs", "tests", "candidates")}
+    # the seeds' expansion here, so that round 0's winners can be counted; the loop takes it from there
+    first = ctx.expand_warped(c, nrm, ref, rounds, **expand)
+    counts["winners0"] = int((first["round"] == 0).sum())
+    ps = ctx.reconstruct_warped(None, None, None, iterations=iterations, rounds=rounds, expand=expand, start=first,
+                                **kw)
+    counts["patches"] = [h["patches"] for h in ps["history"]] + [len(ps["ref"])]
+    colors, nviews = ctx.wpatch_color(ps["c"], ps["ref"], ps["mask"])
+    export2ply_oriented(ps["c"], ps["nrm"], colors, path=path)
+    counts["seconds"] = time.time() - t0
+    print("warped: features {features} pairs {pairs} candidates {candidates} round-0 winners {winners0} "
+          "patches per iteration {patches}".format(**counts))
+    last_stats.clear()
+    last_stats.update(counts)
+    return {"points": ps["c"], "normals": ps["nrm"], "colors": colors, "nviews": nviews, "patches": ps,
+            "counts": counts}
 
 
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):

@@ -71,6 +71,12 @@ SIGNATURES = [
                                                 _vp]),
     ("mvs_wfilt_support", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, _u64p, ctypes.c_int, ctypes.c_double,
                                          ctypes.c_double, ctypes.c_int, _i32p, _i32p, _i32p, _u8p]),
+    ("mvs_wseed_match_device", ctypes.c_int, [_vp, _vp, _i64p, ctypes.c_int64, _i32p, ctypes.c_double,
+                                              ctypes.c_double, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mvs_wseed_match", ctypes.c_int, [_vp, _i32p, _i64p, ctypes.c_int64, _i32p, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_int64, _dp, _dp, _i32p, _i32p, _dp, _i64p]),
+    ("mvs_wpatch_color_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mvs_wpatch_color", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _u64p, _dp, _i32p]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -232,6 +238,23 @@ def triangulate(P1, P2, x1, x2):
     check(load().mvs_triangulate(_p(P1, _dp), _p(P2, _dp), _p(x1, _dp), _p(x2, _dp), _p(out, _dp)),
           what="triangulate")
     return out
+
+
+def seed_view_pairs(Rp, neighbours=4, min_axis_cos=0.5):
+    """The ordered view pairs (r, v) the seed matcher is fed, from the
+    rotations Rp (V,3,3) alone: per r the views v != r ranked by the descending
+    dot product of the optical axes (the third rows of Rp; Python floats, left
+    to right), ties to the lower v; those with a dot >= min_axis_cos; the first
+    `neighbours` of them.  (np, 2) int32, r-major."""
+    ax = [[float(x) for x in row] for row in np.asarray(Rp, np.float64).reshape(-1, 3, 3)[:, 2, :]]
+    V = len(ax)
+    out = []
+    for r in range(V):
+        dots = [(ax[r][0] * ax[v][0] + ax[r][1] * ax[v][1] + ax[r][2] * ax[v][2], v) for v in range(V) if v != r]
+        keep = sorted((d, v) for d, v in dots if d >= float(min_axis_cos))
+        keep.sort(key=lambda dv: (-dv[0], dv[1]))
+        out += [(r, v) for _, v in keep[:max(int(neighbours), 0)]]
+    return np.array(out, np.int32).reshape(-1, 2)
 
 
 # live contexts: a retiring caller stream is announced to each of them
@@ -1485,6 +1508,171 @@ class MvsContext:
         ps["max_dist"] = grow["max_dist"]
         ps["history"] = history
         return ps
+
+    # ---- seeds from image features, patch colours ----
+
+    def wseed_pairs(self, neighbours=4, min_axis_cos=0.5):
+        """The view pairs the seed matcher is fed (seed_view_pairs on the
+        context's rotations): (np, 2) int32, r-major."""
+        return seed_view_pairs(self.rproj(), neighbours, min_axis_cos)
+
+    def _seed_tables(self, feat_off, pairs):
+        feat_off = _c(feat_off, np.int64).reshape(-1)
+        if len(feat_off) != self.V + 1:
+            raise RuntimeError(f"wseed_match: feat_off must have V + 1 = {self.V + 1} entries")
+        pairs = _c(pairs, np.int32).reshape(-1, 2)
+        return feat_off, pairs
+
+    def wseed_match_device(self, feat, feat_off, pairs, epi_px, min_sin2, c, nrm, ref, cand, err, total, stream=None):
+        """mvs_wseed_match_device: feat a torch device tensor (contiguous int32
+        (F,2) [col, row]), feat_off (V+1,) and pairs (np,2) host arrays, the
+        outputs torch device tensors (contiguous: c, nrm float64 (cap,3), ref
+        int32 (cap,), cand int32 (cap,4), err float64 (cap,), total int64 (1,))
+        or, to count only, c = nrm = ref = cand = err = None; stream-ordered."""
+        feat_off, pairs = self._seed_tables(feat_off, pairs)
+        F = int(feat.shape[0])
+        if feat.dtype.itemsize != 4 or tuple(feat.shape) != (F, 2) or not feat.is_contiguous():
+            raise RuntimeError("wseed_match_device: feat must be contiguous int32 (F, 2)")
+        if len(feat_off) and int(feat_off[-1]) > F:
+            raise RuntimeError("wseed_match_device: feat_off names more features than feat holds")
+        outs = [c, nrm, ref, cand, err]
+        cap = 0
+        if any(x is not None for x in outs):
+            cap = int(ref.numel())
+            for name, x, size, shape in [("c", c, 8, (cap, 3)), ("nrm", nrm, 8, (cap, 3)), ("ref", ref, 4, (cap,)),
+                                         ("cand", cand, 4, (cap, 4)), ("err", err, 8, (cap,))]:
+                if x is None or x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                    raise RuntimeError(f"wseed_match_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        if total.dtype.itemsize != 8 or tuple(total.shape) != (1,):
+            raise RuntimeError("wseed_match_device: total must be int64 (1,)")
+        ptr = (lambda x: x.data_ptr() if cap else None)
+        rc = load().mvs_wseed_match_device(self._h, feat.data_ptr(), _p(feat_off, _i64p), len(pairs), _p(pairs, _i32p),
+                                           float(epi_px), float(min_sin2), cap, ptr(c), ptr(nrm), ptr(ref), ptr(cand),
+                                           ptr(err), total.data_ptr(), self._stream_handle(stream))
+        check(rc, self._h, "mvs_wseed_match_device")
+
+    def wseed_match(self, feat, feat_off, pairs, epi_px=1.5, min_sin2=1e-4, cap=None):
+        """Seed candidates from features (mvs_wseed_match, host pointers): every
+        pair (feature a of view r, feature b of view v) of the ordered view
+        pairs whose rays pass each other in front of both cameras, with the point
+        on a's ray within epi_px pixels of b in v, triangulated into a patch
+        (centre on a's ray, normal towards r's camera); the definition is in
+        include/mvs_amd.h.  feat (F,2) int32 [col, row] of all views, feat_off
+        (V+1,), pairs (np,2).  cap None: a counting call first, then room for
+        every candidate.  Returns c (k,3), nrm (k,3), ref (k,) int32, cand (k,4)
+        int32 [pair, a, b, v], err (k,) and the total found (k = min(total, cap))."""
+        feat_off, pairs = self._seed_tables(feat_off, pairs)
+        feat = _c(feat, np.int32).reshape(-1, 2)
+        if len(feat_off) and int(feat_off[-1]) > len(feat):
+            raise RuntimeError("wseed_match: feat_off names more features than feat holds")
+        lib = load()
+        total = np.zeros(1, np.int64)
+
+        def call(cap, c, nrm, ref, cand, err):
+            opt = (lambda x, t: _p(x, t) if cap else None)
+            rc = lib.mvs_wseed_match(self._h, _p(feat, _i32p), _p(feat_off, _i64p), len(pairs), _p(pairs, _i32p),
+                                     float(epi_px), float(min_sin2), int(cap), opt(c, _dp), opt(nrm, _dp),
+                                     opt(ref, _i32p), opt(cand, _i32p), opt(err, _dp), _p(total, _i64p))
+            check(rc, self._h, "mvs_wseed_match")
+
+        if cap is None:
+            call(0, None, None, None, None, None)
+            cap = int(total[0])
+        cap = int(cap)
+        c, nrm = np.empty((max(cap, 1), 3)), np.empty((max(cap, 1), 3))
+        ref, cand = np.empty(max(cap, 1), np.int32), np.empty((max(cap, 1), 4), np.int32)
+        err = np.empty(max(cap, 1))
+        total[0] = 0
+        call(cap, c, nrm, ref, cand, err)
+        k = min(int(total[0]), cap)
+        return c[:k], nrm[:k], ref[:k], cand[:k], err[:k], int(total[0])
+
+    def seed_features(self, border):
+        """harris_points of every view without the points closer than `border`
+        pixels to an image edge: a list of (n_v, 2) int32 [col, row]."""
+        b = int(border)
+        out = []
+        for v in range(self.V):
+            p = self.harris_points(v)
+            out.append(p[(p[:, 0] >= b) & (p[:, 0] <= self.W - 1 - b) & (p[:, 1] >= b) & (p[:, 1] <= self.H - 1 - b)])
+        return out
+
+    def seed_warped(self, feats=None, pairs=None, epi_px=1.5, min_sin2=1e-4, border=None, wid=5):
+        """Seed candidates of the warped pipeline from image features (PMVS's
+        match step): feats None: harris_points per view; the features closer
+        than border (None: wid + 1) to an image edge are dropped; pairs None:
+        wseed_pairs(); then one counting and one emitting wseed_match_device
+        call on the context's side stream.  feats: a list of V arrays (n_v, 2)
+        [col, row].  Returns c (n,3), nrm (n,3), ref (n,) int32, cand (n,4) int32
+        [pair, a, b, v] (a, b index the features kept) and err (n,) as numpy;
+        the counts are left in self.last_seed (features, pairs, tests, candidates)."""
+        import torch
+        border = int(wid) + 1 if border is None else int(border)
+        if feats is None:
+            feats = self.seed_features(border)
+        else:
+            if len(feats) != self.V:
+                raise RuntimeError("seed_warped: feats must hold one array per view")
+            feats = [_c(f, np.int32).reshape(-1, 2) for f in feats]
+            feats = [f[(f[:, 0] >= border) & (f[:, 0] <= self.W - 1 - border) & (f[:, 1] >= border)
+                       & (f[:, 1] <= self.H - 1 - border)] for f in feats]
+        pairs = self.wseed_pairs() if pairs is None else _c(pairs, np.int32).reshape(-1, 2)
+        nv = np.array([len(f) for f in feats], np.int64)
+        feat_off = np.concatenate([[0], np.cumsum(nv)]).astype(np.int64)
+        feat = np.concatenate(feats) if len(feats) else np.empty((0, 2), np.int32)
+        tests = int(sum(int(nv[r]) * int(nv[v]) for r, v in pairs)) if len(pairs) and pairs.min() >= 0 \
+            and pairs.max() < self.V else 0
+        self.last_seed = {"features": int(nv.sum()), "pairs": len(pairs), "tests": tests, "candidates": 0,
+                          "feats": feats}
+        dev = torch.device(f"cuda:{self.device}")
+        st = self._side_stream()
+        with torch.cuda.stream(st):
+            t_feat = torch.from_numpy(_c(feat, np.int32).reshape(-1, 2)).to(dev)
+            total = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.wseed_match_device(t_feat, feat_off, pairs, epi_px, min_sin2, None, None, None, None, None, total,
+                                    stream=st.cuda_stream)
+            n = int(total.item())
+            c = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            nrm = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            ref = torch.empty(n, dtype=torch.int32, device=dev)
+            cand = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            err = torch.empty(n, dtype=torch.float64, device=dev)
+            if n:
+                self.wseed_match_device(t_feat, feat_off, pairs, epi_px, min_sin2, c, nrm, ref, cand, err, total,
+                                        stream=st.cuda_stream)
+            out = tuple(x.cpu().numpy() for x in (c, nrm, ref, cand, err))
+        st.synchronize()
+        self.last_seed["candidates"] = n
+        return out
+
+    def wpatch_color_device(self, c, ref, mask, color, nviews, stream=None):
+        """mvs_wpatch_color_device on torch device tensors (contiguous: c float64
+        (n,3), ref int32 (n,), mask int64 (n,words), color float64 (n,3), nviews
+        int32 (n,)); stream-ordered."""
+        n = int(ref.numel())
+        for name, x, size, shape in [("c", c, 8, (n, 3)), ("ref", ref, 4, (n,)), ("mask", mask, 8, (n, self.words)),
+                                     ("color", color, 8, (n, 3)), ("nviews", nviews, 4, (n,))]:
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wpatch_color_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wpatch_color_device(self._h, n, c.data_ptr(), ref.data_ptr(), mask.data_ptr(),
+                                            color.data_ptr(), nviews.data_ptr(), self._stream_handle(stream))
+        check(rc, self._h, "mvs_wpatch_color_device")
+
+    def wpatch_color(self, c, ref, mask):
+        """The colour of patches (mvs_wpatch_color, host pointers): per channel
+        the mean over the views of {ref} + mask that see the centre of the
+        bilinear sample of the resident RGB image there, in steps of 1/256.
+        Returns color (n,3) float64 (0 where no view sees it) and nviews (n,) int32."""
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        c = _c(c, np.float64).reshape(n, 3)
+        mask = _c(mask, np.uint64).reshape(n, self.words)
+        color = np.zeros((max(n, 1), 3))
+        nviews = np.zeros(max(n, 1), np.int32)
+        rc = load().mvs_wpatch_color(self._h, n, _p(c, _dp), _p(ref, _i32p), _p(mask, _u64p), _p(color, _dp),
+                                     _p(nviews, _i32p))
+        check(rc, self._h, "mvs_wpatch_color")
+        return color[:n], nviews[:n]
 
     def pack_accepted(self, offset, count, mask, vlb, out, stream=None, c=None):
         """mvs_pack_accepted: the accepted candidates (count >= vlb) of a scored

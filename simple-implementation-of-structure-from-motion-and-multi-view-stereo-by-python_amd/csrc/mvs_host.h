@@ -133,6 +133,43 @@ struct Staging {
     }
 };
 
+// Small host tables a stream-ordered *_device call hands to its kernels (the
+// seed matcher's pairs and blocks): a pinned host copy, so the upload is a true
+// asynchronous copy, and the event of the last upload, which the next fill
+// waits for before it rewrites the host copy.
+struct PinnedTable {
+    unsigned char* p = nullptr;
+    size_t n = 0;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    PinnedTable() = default;
+    PinnedTable(const PinnedTable&) = delete;
+    PinnedTable& operator=(const PinnedTable&) = delete;
+    ~PinnedTable() {
+        if (p) (void)hipHostFree(p);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    // room for `bytes`, the previous upload complete
+    unsigned char* fill(size_t bytes) {
+        if (pending) HIPCHK(hipEventSynchronize(ev));
+        pending = false;
+        if (bytes > n) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+            n = 0;
+            HIPCHK(hipHostMalloc((void**)&p, std::max(bytes, (size_t)4096), hipHostMallocDefault));
+            n = std::max(bytes, (size_t)4096);
+        }
+        return p;
+    }
+    void upload(void* dst, size_t bytes, hipStream_t s) {
+        if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIPCHK(hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev, s));
+        pending = true;
+    }
+};
+
 // OpenCV-order geometry (mvs_geometry.cpp)
 void rodrigues_roundtrip(const double* Rin, double* Rout);
 void triangulate(const double* P1, const double* P2, const double* x1, const double* x2, double* X4);
@@ -173,6 +210,10 @@ struct mvs_ctx {
     DevBuf<int64_t> x_offs;
     DevBuf<uint64_t> x_key;
     DevBuf<uint32_t> x_ticket;
+    // the seed matcher's pair and block tables (mvs_wseed_match; it shares
+    // x_cnt, x_offs and wexp_order with the expansion)
+    PinnedTable s_tab_h;
+    DevBuf<unsigned char> s_tab;
     // tiled scorer scratch
     DevBuf<int32_t> t_tiles, t_cand;
     // mvs_pack_accepted: the pack's row counter and chunk ticket (k_acc_pack

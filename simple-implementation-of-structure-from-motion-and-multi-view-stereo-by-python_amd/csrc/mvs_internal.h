@@ -185,6 +185,44 @@ struct WsupArgs {
     uint8_t* keep;          // n
 };
 
+// The seed matcher (mvs_seed_warp.hip; device pointers).  One ordered view pair
+// (r, v): the features of r are feat rows a0 .. a0 + na - 1, those of v are
+// b0 .. b0 + nb - 1; row0 = the features a of the pairs before it (a row of
+// cnt / offs is one (pair, a)).
+struct SeedPair {
+    int32_t r, v;
+    int32_t a0, na;
+    int32_t b0, nb;
+    int64_t row0;
+};
+#define MVS_SEED_BLOCK 256   // features a per workgroup of k_wseed_pairs
+#define MVS_SEED_TILE 256    // features b per LDS tile
+struct WseedArgs {
+    const int32_t* feat;     // F*2 [col, row]
+    const SeedPair* pairs;
+    const int2* blocks;      // (pair, first a) per workgroup, in (pair, a) order
+    int64_t nblocks, rows;   // rows = the sum of na over the pairs
+    double epi2, min_sin2;   // epi_px^2
+    int64_t cap;
+    int32_t* cnt;            // rows
+    int64_t* offs;           // rows + 1
+    double* c;               // cap*3
+    double* nrm;             // cap*3
+    int32_t* ref;            // cap
+    int32_t* cand;           // cap*4 (pair, a, b, v)
+    double* err;             // cap
+    int64_t* total;          // 1
+};
+// The colour of n patches (k_wpatch_color, mvs_seed_warp.hip; device pointers).
+struct WcolArgs {
+    int64_t n;
+    const double* c;         // n*3
+    const int32_t* ref;      // n
+    const uint64_t* mask;    // n*words
+    double* color;           // n*3
+    int32_t* nviews;         // n
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -383,6 +421,11 @@ int mvs_launch_wexp_mark(const SceneDev* sc, const MarkArgs* a, hipStream_t s);
 int mvs_launch_wfilt_front(const SceneDev* sc, const WfiltArgs* a, hipStream_t s);
 int mvs_launch_wfilt_test(const SceneDev* sc, const WfiltArgs* a, hipStream_t s);
 int mvs_launch_wfilt_support(const SceneDev* sc, const WsupArgs* a, hipStream_t s);
+// the seed matcher and the patch colours (mvs_seed_warp.hip): match =
+// k_wseed_pairs count pass, k_wseed_scan, emit pass (none at cap 0); color =
+// k_wpatch_color
+int mvs_launch_wseed_match(const SceneDev* sc, const WseedArgs* a, hipStream_t s);
+int mvs_launch_wpatch_color(const SceneDev* sc, const WcolArgs* a, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

@@ -641,4 +641,186 @@ int mvs_wfilt_support(mvs_ctx* ctx, int64_t n, const double* c, const double* nr
     });
 }
 
+// ---- seeds from features and patch colours (mvs_seed_warp.hip) ----
+
+// the checks of both entry points; *F = the feature total.  0, or the error's code
+static int wseed_check(mvs_ctx* ctx, const int64_t* feat_off, int64_t np, const int32_t* pairs, double epi_px,
+                       double min_sin2, int64_t cap, int64_t* F) {
+    const char* who = "mvs_wseed_match";
+    if (int rc = need_nonneg(ctx, who, "np", np)) return rc;
+    if (np >= ((int64_t)1 << 31)) return bad_arg(ctx, who, "np must be below 2^31");
+    if (int rc = need_nonneg(ctx, who, "cap", cap)) return rc;
+    if (!(epi_px > 0.0 && epi_px < HUGE_VAL)) return bad_arg(ctx, who, "epi_px must be finite and > 0");
+    if (!(min_sin2 >= 0.0 && min_sin2 < 1.0)) return bad_arg(ctx, who, "min_sin2 must be in [0, 1)");
+    *F = 0;
+    if (np == 0) return 0;
+    if (!feat_off || !pairs) return bad_arg(ctx, who, "null pointer (feat_off, pairs)");
+    const int V = ctx->V;
+    if (feat_off[0] != 0) return bad_arg(ctx, who, "feat_off[0] must be 0");
+    for (int v = 0; v < V; ++v)
+        if (feat_off[v + 1] < feat_off[v]) return bad_arg(ctx, who, "feat_off decreases");
+    if (feat_off[V] >= ((int64_t)1 << 31)) return bad_arg(ctx, who, "more than 2^31 - 1 features");
+    for (int64_t k = 0; k < np; ++k) {
+        const int32_t r = pairs[2 * k], v = pairs[2 * k + 1];
+        if (r < 0 || r >= V || v < 0 || v >= V) return bad_arg(ctx, who, "pair view out of range");
+        if (r == v) return bad_arg(ctx, who, "pair of a view with itself");
+    }
+    *F = feat_off[V];
+    return 0;
+}
+
+// the call on device pointers (F > 0, np > 0, arguments checked)
+static void wseed_launch(mvs_ctx* ctx, const int32_t* d_feat, const int64_t* feat_off, int64_t np,
+                         const int32_t* pairs, double epi_px, double min_sin2, int64_t cap, double* d_c,
+                         double* d_nrm, int32_t* d_ref, int32_t* d_cand, double* d_err, int64_t* d_total,
+                         hipStream_t s) {
+    int64_t rows = 0, nblocks = 0;
+    for (int64_t k = 0; k < np; ++k) {
+        const int64_t na = feat_off[pairs[2 * k] + 1] - feat_off[pairs[2 * k]];
+        rows += na;
+        nblocks += (na + MVS_SEED_BLOCK - 1) / MVS_SEED_BLOCK;
+    }
+    if (rows >= ((int64_t)1 << 31) || nblocks >= ((int64_t)1 << 31))
+        throw Fail{MVS_E_ARG, "mvs_wseed_match: the pairs' reference features sum to 2^31 or more"};
+    ctx->wexp_order.acquire(s);
+    const size_t bytes = (size_t)np * sizeof(SeedPair) + (size_t)nblocks * sizeof(int2);
+    unsigned char* h = ctx->s_tab_h.fill(bytes);
+    SeedPair* hp = (SeedPair*)h;
+    int2* hb = (int2*)(h + (size_t)np * sizeof(SeedPair));
+    int64_t row = 0, blk = 0;
+    for (int64_t k = 0; k < np; ++k) {
+        const int32_t r = pairs[2 * k], v = pairs[2 * k + 1];
+        SeedPair p{};
+        p.r = r;
+        p.v = v;
+        p.a0 = (int32_t)feat_off[r];
+        p.na = (int32_t)(feat_off[r + 1] - feat_off[r]);
+        p.b0 = (int32_t)feat_off[v];
+        p.nb = (int32_t)(feat_off[v + 1] - feat_off[v]);
+        p.row0 = row;
+        hp[k] = p;
+        row += p.na;
+        for (int32_t a0 = 0; a0 < p.na; a0 += MVS_SEED_BLOCK) hb[blk++] = make_int2((int)k, a0);
+    }
+    ctx->s_tab.ensure(bytes);
+    ctx->x_cnt.ensure((size_t)rows);
+    ctx->x_offs.ensure((size_t)rows + 1);
+    ctx->s_tab_h.upload(ctx->s_tab.p, bytes, s);
+    WseedArgs a{};
+    a.feat = d_feat;
+    a.pairs = (const SeedPair*)ctx->s_tab.p;
+    a.blocks = (const int2*)(ctx->s_tab.p + (size_t)np * sizeof(SeedPair));
+    a.nblocks = nblocks;
+    a.rows = rows;
+    a.epi2 = epi_px * epi_px;
+    a.min_sin2 = min_sin2;
+    a.cap = cap;
+    a.cnt = ctx->x_cnt.p;
+    a.offs = ctx->x_offs.p;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.cand = d_cand;
+    a.err = d_err;
+    a.total = d_total;
+    if (mvs_launch_wseed_match(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wseed_match launch failed"};
+    ctx->wexp_order.release(s);
+}
+
+int mvs_wseed_match_device(mvs_ctx* ctx, const int32_t* d_feat, const int64_t* feat_off, int64_t np,
+                           const int32_t* pairs, double epi_px, double min_sin2, int64_t cap, double* d_c,
+                           double* d_nrm, int32_t* d_ref, int32_t* d_cand, double* d_err, int64_t* d_total,
+                           void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    int64_t F = 0;
+    if (int rc = wseed_check(ctx, feat_off, np, pairs, epi_px, min_sin2, cap, &F)) return rc;
+    if (np == 0 || F == 0) return MVS_OK;
+    if (!d_feat || !d_total || (cap > 0 && (!d_c || !d_nrm || !d_ref || !d_cand || !d_err)))
+        return bad_arg(ctx, "mvs_wseed_match", "null pointer (the outputs may be NULL when cap is 0)");
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wseed_launch(ctx, d_feat, feat_off, np, pairs, epi_px, min_sin2, cap, d_c, d_nrm, d_ref, d_cand, d_err,
+                     d_total, s);
+        return 0;
+    });
+}
+
+int mvs_wseed_match(mvs_ctx* ctx, const int32_t* feat, const int64_t* feat_off, int64_t np, const int32_t* pairs,
+                    double epi_px, double min_sin2, int64_t cap, double* c, double* nrm, int32_t* ref,
+                    int32_t* cand, double* err, int64_t* total) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    int64_t F = 0;
+    if (int rc = wseed_check(ctx, feat_off, np, pairs, epi_px, min_sin2, cap, &F)) return rc;
+    if (np == 0 || F == 0) return MVS_OK;
+    if (!feat || !total || (cap > 0 && (!c || !nrm || !ref || !cand || !err)))
+        return bad_arg(ctx, "mvs_wseed_match", "null pointer (the outputs may be NULL when cap is 0)");
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_feat = st.in(feat, F * 2);
+        const auto d_c = st.out(cap ? c : nullptr, cap * 3);
+        const auto d_nrm = st.out(cap ? nrm : nullptr, cap * 3);
+        const auto d_err = st.out(cap ? err : nullptr, cap);
+        const auto d_total = st.out(total, 1);
+        const auto d_ref = st.out(cap ? ref : nullptr, cap);
+        const auto d_cand = st.out(cap ? cand : nullptr, cap * 4);
+        st.upload();
+        wseed_launch(ctx, d_feat, feat_off, np, pairs, epi_px, min_sin2, cap, d_c, d_nrm, d_ref, d_cand, d_err,
+                     d_total, s);
+        st.finish();
+        return 0;
+    });
+}
+
+static int wcol_check(mvs_ctx* ctx, int64_t n, bool ptrs_ok) {
+    if (int rc = need_nonneg(ctx, "mvs_wpatch_color", "n", n)) return rc;
+    if (n >= ((int64_t)1 << 31)) return bad_arg(ctx, "mvs_wpatch_color", "n must be below 2^31");
+    if (n > 0 && !ptrs_ok) return bad_arg(ctx, "mvs_wpatch_color", "null pointer");
+    return 0;
+}
+
+static void wcol_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref, const uint64_t* d_mask,
+                        double* d_color, int32_t* d_nviews, hipStream_t s) {
+    WcolArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.color = d_color;
+    a.nviews = d_nviews;
+    if (mvs_launch_wpatch_color(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wpatch_color launch failed"};
+}
+
+int mvs_wpatch_color_device(mvs_ctx* ctx, int64_t n, const double* d_c, const int32_t* d_ref, const uint64_t* d_mask,
+                            double* d_color, int32_t* d_nviews, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wcol_check(ctx, n, d_c && d_ref && d_mask && d_color && d_nviews)) return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wcol_launch(ctx, n, d_c, d_ref, d_mask, d_color, d_nviews, s);
+        return 0;
+    });
+}
+
+int mvs_wpatch_color(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, const uint64_t* mask,
+                     double* color, int32_t* nviews) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wcol_check(ctx, n, c && ref && mask && color && nviews)) return rc;
+    if (n == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_mask = st.in(mask, n * ctx->words());
+        const auto d_ref = st.in(ref, n);
+        const auto d_color = st.out(color, n * 3);
+        const auto d_nviews = st.out(nviews, n);
+        st.upload();
+        wcol_launch(ctx, n, d_c, d_ref, d_mask, d_color, d_nviews, s);
+        st.finish();
+        return 0;
+    });
+}
+
 }  // extern "C"

@@ -70,6 +70,38 @@ def read_ply(path):
     return np.frombuffer(raw[end:], "<f8", count=n * 6).reshape(n, 6).copy()
 
 
+def export2ply_oriented(points, normals, colors, path="output"):
+    """Write path + '.ply' with double properties x y z nx ny nz red green blue
+    (binary little-endian): an oriented point cloud."""
+    pts = np.asarray(points, np.float64).reshape(-1, 3)
+    nrm = np.asarray(normals, np.float64).reshape(-1, 3)
+    col = np.asarray(colors).reshape(-1, 3).astype(np.float64)
+    if not len(pts) == len(nrm) == len(col):
+        raise RuntimeError("export2ply_oriented: points, normals and colors differ in length")
+    data = np.hstack((pts, nrm, col))
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(data)}\n"
+              + "".join(f"property double {p}\n" for p in ("x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"))
+              + "end_header\n")
+    with open(path + ".ply", "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(np.ascontiguousarray(data, "<f8").tobytes())
+
+
+def read_ply_oriented(path):
+    """Inverse of export2ply_oriented: (points, normals, colors), (n, 3) float64 each."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode().splitlines()
+    n = int([ln for ln in head if ln.startswith("element vertex")][0].split()[-1])
+    props = [ln.split()[1:] for ln in head if ln.startswith("property")]
+    if props != [["double", p] for p in ("x", "y", "z", "nx", "ny", "nz", "red", "green", "blue")]:
+        raise RuntimeError(f"{path}: not an oriented point cloud of export2ply_oriented")
+    rows = np.frombuffer(raw[end:], "<f8", count=n * 9).reshape(n, 9).copy()
+    return rows[:, :3], rows[:, 3:6], rows[:, 6:]
+
+
 def tracks_to_arrays(tracks):
     """[track.point2d_list = [(view, x, y), ...]] -> (track_off i64, obs_view i32, obs_xy f32)."""
     off, view, xy = [0], [], []

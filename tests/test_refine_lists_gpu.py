@@ -8,8 +8,9 @@ unless both are nan.  No row is left out.
 
 Sizes: one wave per row, four rows per workgroup (n around 4 and 256 * 4 + 1);
 lane = view, one key per lane and group of 64 views (V = 64, 65, 80 and 256: a
-full group, one view past it, a partial second group, four groups; V = 1 and 2
-lie below every max_views).
+full group, one view past it, a partial second group, four groups; V = 129,
+192 and 193: the three-group instantiation, partial and full, and one view into
+the fourth group; V = 1 and 2 lie below every max_views).
 """
 import ctypes
 import os
@@ -140,7 +141,7 @@ def crafted_ncc(V, n=40, seed=0):
     return ncc
 
 
-@pytest.mark.parametrize("V", [1, 2, 24, 64, 65, 80, 256])
+@pytest.mark.parametrize("V", [1, 2, 24, 64, 65, 80, 129, 192, 193, 256])
 def test_rule_on_crafted_ncc(pkg, sphere, V):
     if V == 24:
         s, own = sphere, False

@@ -169,17 +169,17 @@ def warped_batch(gray, K, Rp, t, c, nrm, ref, wid=5, min_cos=0.0):
     return {k: np.array([r[k] for r in rs]) for k in ("xy", "valid", "ncc", "sigma_b", "border", "cosm")}
 
 
-def sphere_patches(K, R, t, n, rad, rng, shifts=(0.0,), H=96, W=128, min_facing=0.5):
+def sphere_patches(K, R, t, n, rad, rng, shifts=(0.0,), H=96, W=128, min_facing=0.5, margin=8):
     """n patches of the sphere |X| = rad facing their reference camera: a random
-    view, a random pixel whose ray (par-file rotation R) hits the sphere, the
-    first hit, kept when the outward normal and the direction to the camera
+    view, a random pixel (at least margin px from the border) whose ray
+    (par-file rotation R) hits the sphere, the first hit, kept when the outward normal and the direction to the camera
     make a cosine above min_facing.  Patch k is moved by shifts[k % len(shifts)]
     along its normal.  -> c (n,3), nrm (n,3) true normals, ref (n,), shift (n,)."""
     V = len(K)
     c, nr, ref, sh = [], [], [], []
     while len(c) < n:
         v = int(rng.integers(0, V))
-        x, y = rng.uniform(8, W - 8), rng.uniform(8, H - 8)
+        x, y = rng.uniform(margin, W - margin), rng.uniform(margin, H - margin)
         d = R[v].T @ (np.linalg.inv(K[v]) @ np.array([x, y, 1.0]))
         d /= np.linalg.norm(d)
         O = -R[v].T @ t[v]

@@ -523,6 +523,95 @@ int mvs_wpatch_color_device(mvs_ctx* ctx, int64_t n, const double* d_c, const in
 /* Same on host pointers; synchronous. */
 int mvs_wpatch_color(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* ref, const uint64_t* mask,
                      double* color, int32_t* nviews);
+/* ---- Depth maps of a warped patch set ----
+ * (no reference counterpart).  The far end of the warped pipeline: per-pixel
+ * depth and patch-index maps of the views, rendered from the oriented patches
+ * by a z-buffer splat; the count of the other views that agree with, or see
+ * through, every pixel's depth; and the world points and colours of listed
+ * pixels.  Three stream-ordered device calls; the chain that fuses the maps
+ * into a dense cloud is MvsContext.depth_maps.  Cameras (Rp, t, fx fy cx cy,
+ * O_v = -Rp_v^T t_v), "projection" (x, y, depth as mvs_score gives them), T(p)
+ * = {ref_p} U {v : mask bit v} and the dead rows (ref outside 0..V-1) are the
+ * visibility filter's above, word for word; mask bits >= V are ignored.
+ * Integer coordinates are pixel centres.  All arithmetic is binary64, products
+ * and sums left to right, unfused, so every output is defined to the bit.
+ * Maps cover a contiguous view range v0 .. v0 + nv - 1 inside 0..V-1 (nv >= 1),
+ * are laid out [v - v0][y][x] (nv H W elements) and belong to the caller; no
+ * call keeps context state, so each runs on any stream beside any other call.
+ * The ray of the integer pixel q of view v: d = Rp_v^T ((q.x - cx_v) / fx_v,
+ * (q.y - cy_v) / fy_v, 1), d[k] = Rp[k] u + Rp[3 + k] w + Rp[6 + k] (step 4 of
+ * mvs_wexp_children); it has camera z = 1, so a parameter along it is a depth.
+ *
+ * mvs_wdepth_splat_device: n patches, n < 2^31 (c, nrm, ref, mask), radius R in
+ * 0..3, slope finite and > 0.  For every live patch p and every v in T(p)
+ * inside the range:
+ *   1. (x, y, z) = projection of c_p into v; skipped unless z > 0, 0 <= x < W
+ *      and 0 <= y < H.  z = Rp_v[6] X + Rp_v[7] Y + Rp_v[8] Z + t_v[2], the
+ *      filter's z_p(v).
+ *   2. Skipped unless nrm_p.(O_v - c_p) > 0 (the difference first, then the dot
+ *      product left to right): a back-facing patch draws nothing.
+ *   3. (x0, y0) = (int(x + 0.5), int(y + 0.5)); the footprint is the integer
+ *      pixels q with |q.x - x0| <= R and |q.y - y0| <= R inside the image.
+ *   4. For each q: den = nrm_p.d(q), s = (nrm_p.(c_p - O_v)) / den; skipped
+ *      unless den != 0, s is finite and > 0 and |s - z| <= slope (m + 1) z /
+ *      ((fx_v + fy_v) / 2) with m = max(|q.x - x0|, |q.y - y0|), the right side
+ *      evaluated left to right: a depth change of `slope` pixel footprints per
+ *      pixel, which removes the blow-up of grazing planes.  s is the depth of
+ *      the patch plane at q.
+ *   5. zmap[v][q] (binary64) = the least s over all contributions, idmap[v][q]
+ *      (int32) = the lowest p among those with exactly that s.  A pixel nobody
+ *      reaches holds +inf and -1.
+ * Every element of both maps is written (n = 0 still fills them): k_wdepth_fill,
+ * then k_wdepth_splat twice -- a 64-bit atomic min of s's bit pattern, then an
+ * unsigned 32-bit atomic min of the index among the holders of the minimum
+ * (mvs_wfilt_front's idiom; the result does not depend on scheduling).  One
+ * wave per patch; the (view, footprint pixel) pairs of a patch are flattened
+ * over the lanes, 64 per pass.
+ *
+ * mvs_wdepth_consist_device: a zmap as given (it need not come from the splat),
+ * rel_tol finite and >= 0; cons and viol are uint8 per pixel (viol may be
+ * NULL).  For a pixel (v, q) whose z = zmap[v][q] is finite and > 0:
+ *   1. X = O_v + z d(q), each component one product and one sum.
+ *   2. For every other view u of the range, ascending: (x, y, depth) =
+ *      projection of X into u; u is skipped unless depth > 0, x >= 0, y >= 0,
+ *      int(x + 0.5) < W and int(y + 0.5) < H.
+ *   3. zu = zmap[u][int(y + 0.5)][int(x + 0.5)].  A zu that is not finite
+ *      (a hole, or nan) is unknown and counts nowhere.
+ *   4. (v, q) is consistent with u when |zu - depth| <= rel_tol depth, and a
+ *      violation (u sees through X) when zu - depth > rel_tol depth; a smaller
+ *      zu is an occlusion and counts nowhere.  rel_tol depth is one product.
+ * cons = the number of consistent views, viol = the number of violations; every
+ * other pixel gets 0 and 0.  V <= 256, so a count never saturates.  One thread
+ * per pixel (k_wdepth_consist), the other views a wave-uniform loop.
+ *
+ * mvs_wdepth_points_device: m listed pixels, m < 2^31, as int32 triples (v, q.x,
+ * q.y) inside the range and the image.  xyz[3k..] = X as above from zmap[v][q]
+ * and rgb[3k..] = the 3 bytes of the resident RGB image of view v at q; a pixel
+ * whose z is not finite and > 0 yields nan (the quiet nan 0x7ff8000000000000)
+ * and 0.  The device call reads nothing for a triple outside the range or the
+ * image and writes nan and 0; the host-pointer call refuses it.  m = 0 returns
+ * MVS_OK and launches nothing (k_wdepth_points, one thread per pixel).
+ *
+ * MVS_E_ARG (message in mvs_last_error) for a scalar out of range, a NULL
+ * pointer (the patch rows may be NULL when n = 0, the pixel rows when m = 0),
+ * n or m < 0 or >= 2^31, or a view range outside 0..V-1.  The host-pointer
+ * variants are synchronous, on the context's stream and the staging buffer
+ * that every host-pointer call of the context shares.  Stream-ordered (NULL =
+ * the context's stream). */
+int mvs_wdepth_splat_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm,
+                            const int32_t* d_ref, const uint64_t* d_mask, int radius, double slope, int v0,
+                            int nv, double* d_zmap, int32_t* d_idmap, void* stream);
+int mvs_wdepth_splat(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                     const uint64_t* mask, int radius, double slope, int v0, int nv, double* zmap,
+                     int32_t* idmap);
+int mvs_wdepth_consist_device(mvs_ctx* ctx, const double* d_zmap, int v0, int nv, double rel_tol,
+                              uint8_t* d_cons, uint8_t* d_viol, void* stream);
+int mvs_wdepth_consist(mvs_ctx* ctx, const double* zmap, int v0, int nv, double rel_tol, uint8_t* cons,
+                       uint8_t* viol);
+int mvs_wdepth_points_device(mvs_ctx* ctx, int64_t m, const int32_t* d_pix, const double* d_zmap, int v0,
+                             int nv, double* d_xyz, uint8_t* d_rgb, void* stream);
+int mvs_wdepth_points(mvs_ctx* ctx, int64_t m, const int32_t* pix, const double* zmap, int v0, int nv,
+                      double* xyz, uint8_t* rgb);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

@@ -21,6 +21,10 @@ Harris features along epipolar lines, expand -> filter) and writes
 warped_patches.ply, an oriented point cloud; it needs neither SfM nor -seeds:
 
     python main.py -img_p data/dinoRing -par_p data/dinoRing/dinoR_par.txt -t png --warped
+
+With -depth_maps DIR [-depth_radius R] it also renders per-view depth and normal
+maps from the patches (DIR/depth_%04d.npy, DIR/normal_%04d.npy) and writes the
+dense cloud fused from them as warped_dense.ply.
 """
 import importlib
 import os
@@ -50,7 +54,8 @@ def main(args, threshold=0.01, MIN_REPROJECTION_ERROR=0.3):
         # features along epipolar lines, expand -> filter, warped_patches.ply
         # with normals (MVS2.DensePointsWarped); single process
         mvs.DensePointsWarped(imgs, args, rounds=args.warped_rounds, iterations=args.warped_iterations,
-                              epi_px=args.epi_px, expand={"cell_size": args.cell_size})
+                              epi_px=args.epi_px, expand={"cell_size": args.cell_size},
+                              depth_maps=args.depth_maps, depth_radius=args.depth_radius)
         return
     if getattr(args, "seeds", None):
         global_set = mvs.SeedSet.load(args.seeds)
@@ -100,6 +105,11 @@ if __name__ == "__main__":
                         help="--warped: filter / resumption iterations")
     parser.add_argument("-epi_px", dest="epi_px", default=1.5, type=float,
                         help="--warped: the seed matcher's distance from the epipolar line, pixels")
+    parser.add_argument("-depth_maps", dest="depth_maps", default=None,
+                        help="--warped: a directory for per-view depth_%%04d.npy and normal_%%04d.npy maps; the "
+                             "cloud fused from them goes to warped_dense.ply")
+    parser.add_argument("-depth_radius", dest="depth_radius", default=1, type=int,
+                        help="--warped -depth_maps: the splat's footprint radius in pixels, 0..3")
     args = parser.parse_args()
     try:
         main(args)

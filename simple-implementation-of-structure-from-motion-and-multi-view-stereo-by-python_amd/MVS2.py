@@ -9,6 +9,7 @@ MyPatch.photo_consistenecy_test(...)          MVS2.py:62-77
     Same method on the same fields; one-candidate call of the batched GPU
     scorer.  Use photo_consistency_batch for many candidates.
 """
+import os
 import sys
 import time
 import zlib
@@ -156,8 +157,30 @@ def reconstruct_patches_warped(ctx, centroids, normals, ref_views, **kw):
     return ctx.reconstruct_warped(centroids, normals, ref_views, **kw)
 
 
+def depth_maps_warped(ctx, patches, **kw):
+    """Per-view depth and normal maps of a warped patch set and the dense cloud
+    fused from them (no reference counterpart; see MvsContext.depth_maps, which
+    takes the keywords): `patches` is the dict expand_patches_warped,
+    filter_patches_warped or reconstruct_patches_warped returns."""
+    return ctx.depth_maps(patches, **kw)
+
+
+def write_depth_maps(maps, directory, first_view=0, dense_path="warped_dense"):
+    """The files of a depth_maps_warped result: directory/depth_%04d.npy (H,W)
+    float32, nan for empty pixels, and directory/normal_%04d.npy (H,W,3)
+    float32 per view, and the fused cloud as dense_path + '.ply'
+    (export2ply_oriented)."""
+    os.makedirs(directory, exist_ok=True)
+    for k in range(len(maps["z"])):
+        z = np.where(np.isfinite(maps["z"][k]), maps["z"][k], np.nan).astype(np.float32)
+        np.save(os.path.join(directory, "depth_%04d.npy" % (first_view + k)), z)
+        np.save(os.path.join(directory, "normal_%04d.npy" % (first_view + k)), maps["normal"][k].astype(np.float32))
+    export2ply_oriented(maps["points"], maps["normals"], maps["colors"], path=dense_path)
+
+
 def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1e-4, neighbours=4, min_axis_cos=0.5,
-                      feats=None, pairs=None, path="warped_patches", device=None, **kw):
+                      feats=None, pairs=None, path="warped_patches", device=None, depth_maps=None, depth_radius=1,
+                      dense_path="warped_dense", **kw):
     """An oriented, coloured point cloud from calibrated images alone (no
     reference counterpart; PMVS's match -> expand -> filter on the warped
     pipeline, without SfM tracks):
@@ -174,6 +197,13 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
       4. MvsContext.wpatch_color of the final set;
       5. export2ply_oriented -> path + '.ply' (points, normals, colours);
       6. one line of counts.
+
+    depth_maps (a directory, default None: nothing more happens): after step 5,
+    MvsContext.depth_maps of the final set at radius depth_radius, written by
+    write_depth_maps -- depth_%04d.npy and normal_%04d.npy per view into the
+    directory and the fused cloud as dense_path + '.ply'; the count line and
+    the counts gain "dense", the number of fused points, and the returned dict
+    gains "maps".
 
     Returns a dict: points, normals, colors (n,3), nviews, patches (the final
     set as reconstruct_warped returns it) and counts (features, pairs, tests,
@@ -196,13 +226,21 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
     counts["patches"] = [h["patches"] for h in ps["history"]] + [len(ps["ref"])]
     colors, nviews = ctx.wpatch_color(ps["c"], ps["ref"], ps["mask"])
     export2ply_oriented(ps["c"], ps["nrm"], colors, path=path)
+    maps = None
+    if depth_maps is not None:
+        maps = ctx.depth_maps(ps, radius=depth_radius)
+        write_depth_maps(maps, depth_maps, dense_path=dense_path)
+        counts["dense"] = len(maps["points"])
     counts["seconds"] = time.time() - t0
     print("warped: features {features} pairs {pairs} candidates {candidates} round-0 winners {winners0} "
-          "patches per iteration {patches}".format(**counts))
+          "patches per iteration {patches}".format(**counts) + (" dense {dense}".format(**counts) if maps else ""))
     last_stats.clear()
     last_stats.update(counts)
-    return {"points": ps["c"], "normals": ps["nrm"], "colors": colors, "nviews": nviews, "patches": ps,
-            "counts": counts}
+    out = {"points": ps["c"], "normals": ps["nrm"], "colors": colors, "nviews": nviews, "patches": ps,
+           "counts": counts}
+    if maps is not None:
+        out["maps"] = maps
+    return out
 
 
 def DensePointsWithMVS2(imgs, global_set, args, max_pops=100000, device=None):

@@ -77,6 +77,16 @@ SIGNATURES = [
                                        ctypes.c_int64, _dp, _dp, _i32p, _i32p, _dp, _i64p]),
     ("mvs_wpatch_color_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mvs_wpatch_color", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _i32p, _u64p, _dp, _i32p]),
+    ("mvs_wdepth_splat_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_double,
+                                               ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
+    ("mvs_wdepth_splat", ctypes.c_int, [_vp, ctypes.c_int64, _dp, _dp, _i32p, _u64p, ctypes.c_int, ctypes.c_double,
+                                        ctypes.c_int, ctypes.c_int, _dp, _i32p]),
+    ("mvs_wdepth_consist_device", ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp,
+                                                 _vp]),
+    ("mvs_wdepth_consist", ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _u8p, _u8p]),
+    ("mvs_wdepth_points_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                                _vp]),
+    ("mvs_wdepth_points", ctypes.c_int, [_vp, ctypes.c_int64, _i32p, _dp, ctypes.c_int, ctypes.c_int, _dp, _u8p]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -1673,6 +1683,171 @@ class MvsContext:
                                      _p(nviews, _i32p))
         check(rc, self._h, "mvs_wpatch_color")
         return color[:n], nviews[:n]
+
+    def _view_range(self, views):
+        """(v0, nv) of a view range given as None (every view) or (v0, nv)."""
+        v0, nv = (0, self.V) if views is None else (int(views[0]), int(views[1]))
+        if v0 < 0 or nv < 1 or v0 + nv > self.V:
+            raise RuntimeError("the view range (v0, nv) must lie inside 0..V-1, nv >= 1")
+        return v0, nv
+
+    def wdepth_splat_device(self, c, nrm, ref, mask, radius, slope, v0, nv, zmap, idmap, stream=None):
+        """mvs_wdepth_splat_device on torch device tensors (contiguous: c, nrm
+        float64 (n,3), ref int32 (n,), mask int64 (n,words), zmap float64 and
+        idmap int32 (nv,H,W), both written whole); stream-ordered."""
+        n = int(ref.numel())
+        maps = (int(nv), self.H, self.W)
+        for name, x, size, shape in [("c", c, 8, (n, 3)), ("nrm", nrm, 8, (n, 3)), ("ref", ref, 4, (n,)),
+                                     ("mask", mask, 8, (n, self.words)), ("zmap", zmap, 8, maps),
+                                     ("idmap", idmap, 4, maps)]:
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wdepth_splat_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wdepth_splat_device(self._h, n, c.data_ptr(), nrm.data_ptr(), ref.data_ptr(), mask.data_ptr(),
+                                            int(radius), float(slope), int(v0), int(nv), zmap.data_ptr(),
+                                            idmap.data_ptr(), self._stream_handle(stream))
+        check(rc, self._h, "mvs_wdepth_splat_device")
+
+    def wdepth_consist_device(self, zmap, v0, nv, rel_tol, cons, viol=None, stream=None):
+        """mvs_wdepth_consist_device on torch device tensors (contiguous: zmap
+        float64, cons and viol uint8 (nv,H,W); viol may be None); stream-ordered."""
+        maps = (int(nv), self.H, self.W)
+        for name, x, size in [("zmap", zmap, 8), ("cons", cons, 1), ("viol", viol, 1)]:
+            if x is not None and (x.dtype.itemsize != size or tuple(x.shape) != maps or not x.is_contiguous()):
+                raise RuntimeError(f"wdepth_consist_device: {name} must be contiguous, {size}-byte elements, {maps}")
+        rc = load().mvs_wdepth_consist_device(self._h, zmap.data_ptr(), int(v0), int(nv), float(rel_tol),
+                                              cons.data_ptr(), viol.data_ptr() if viol is not None else None,
+                                              self._stream_handle(stream))
+        check(rc, self._h, "mvs_wdepth_consist_device")
+
+    def wdepth_points_device(self, pix, zmap, v0, nv, xyz, rgb, stream=None):
+        """mvs_wdepth_points_device on torch device tensors (contiguous: pix int32
+        (m,3) rows (view, x, y), zmap float64 (nv,H,W), xyz float64 (m,3), rgb
+        uint8 (m,3)); stream-ordered."""
+        m = int(pix.shape[0])
+        for name, x, size, shape in [("pix", pix, 4, (m, 3)), ("zmap", zmap, 8, (int(nv), self.H, self.W)),
+                                     ("xyz", xyz, 8, (m, 3)), ("rgb", rgb, 1, (m, 3))]:
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wdepth_points_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wdepth_points_device(self._h, m, pix.data_ptr(), zmap.data_ptr(), int(v0), int(nv),
+                                             xyz.data_ptr(), rgb.data_ptr(), self._stream_handle(stream))
+        check(rc, self._h, "mvs_wdepth_points_device")
+
+    def wdepth_splat(self, c, nrm, ref, mask, radius=1, slope=4.0, views=None):
+        """Depth and patch-index maps of a patch set (mvs_wdepth_splat, host
+        pointers): zmap (nv,H,W) float64 (+inf = empty) and idmap int32 (-1)."""
+        v0, nv = self._view_range(views)
+        ref = _c(ref, np.int32).reshape(-1)
+        n = len(ref)
+        c = _c(c, np.float64).reshape(n, 3)
+        nrm = _c(nrm, np.float64).reshape(n, 3)
+        mask = _c(mask, np.uint64).reshape(n, self.words)
+        zmap = np.empty((nv, self.H, self.W), np.float64)
+        idmap = np.empty((nv, self.H, self.W), np.int32)
+        rc = load().mvs_wdepth_splat(self._h, n, _p(c, _dp), _p(nrm, _dp), _p(ref, _i32p), _p(mask, _u64p),
+                                     int(radius), float(slope), v0, nv, _p(zmap, _dp), _p(idmap, _i32p))
+        check(rc, self._h, "mvs_wdepth_splat")
+        return zmap, idmap
+
+    def wdepth_consist(self, zmap, rel_tol=0.01, views=None):
+        """The cross-view consistency count of depth maps (mvs_wdepth_consist,
+        host pointers) -> cons, viol (nv,H,W) uint8."""
+        v0, nv = self._view_range(views)
+        zmap = _c(zmap, np.float64).reshape(nv, self.H, self.W)
+        cons = np.empty((nv, self.H, self.W), np.uint8)
+        viol = np.empty((nv, self.H, self.W), np.uint8)
+        rc = load().mvs_wdepth_consist(self._h, _p(zmap, _dp), v0, nv, float(rel_tol), _p(cons, _u8p), _p(viol, _u8p))
+        check(rc, self._h, "mvs_wdepth_consist")
+        return cons, viol
+
+    def wdepth_points(self, pix, zmap, views=None):
+        """World points and colours of listed pixels (mvs_wdepth_points, host
+        pointers; a pixel outside the range or the image raises) -> xyz (m,3)
+        float64 and rgb (m,3) uint8."""
+        v0, nv = self._view_range(views)
+        pix = _c(pix, np.int32).reshape(-1, 3)
+        m = len(pix)
+        zmap = _c(zmap, np.float64).reshape(nv, self.H, self.W)
+        xyz = np.zeros((max(m, 1), 3))
+        rgb = np.zeros((max(m, 1), 3), np.uint8)
+        rc = load().mvs_wdepth_points(self._h, m, _p(pix, _i32p), _p(zmap, _dp), v0, nv, _p(xyz, _dp), _p(rgb, _u8p))
+        check(rc, self._h, "mvs_wdepth_points")
+        return xyz[:m], rgb[:m]
+
+    def depth_maps(self, patches, radius=1, slope=4.0, views=None, rel_tol=0.01, min_consistent=2, max_violations=0,
+                   timer=None):
+        """Per-view depth and normal maps of a warped patch set and the dense
+        cloud fused from them (the definitions are in include/mvs_amd.h).
+        `patches` is the dict expand_warped, filter_warped or reconstruct_warped
+        returns; it needs c, nrm, ref and mask.  views: None (every view) or
+        (v0, nv).  The maps are splatted (wdepth_splat_device), the other views
+        that agree with or see through each pixel are counted
+        (wdepth_consist_device), and a pixel (v, q) is fused when id >= 0,
+        ref[id] = v, cons >= min_consistent and viol <= max_violations: the ref
+        rule emits a surface point once, in its patch's reference view.  The
+        fused points and colours come from wdepth_points_device; selection and
+        gathers are torch indexing on the device.  Everything runs on the
+        context's torch side stream.
+
+        Returns a dict of numpy arrays: z (nv,H,W) float64 (+inf = empty), id
+        int32 (-1), cons and viol uint8, normal (nv,H,W,3) float64 (nan where
+        empty), and the fused cloud points (m,3), normals (m,3), colors (m,3)
+        uint8 and pix (m,3) int32 rows (view, x, y) in the maps' order.
+        timer: an optional callable timer(phase, 0) called on the chain's stream
+        before each phase ("splat", "consist", "select", "points") and with
+        phase "end" after the last."""
+        import torch
+        for k in ("c", "nrm", "ref", "mask"):
+            if k not in patches:
+                raise RuntimeError(f"depth_maps: patches has no '{k}'")
+        v0, nv = self._view_range(views)
+        ref0 = _c(patches["ref"], np.int32).reshape(-1)
+        n = len(ref0)
+        c0 = _c(patches["c"], np.float64).reshape(n, 3)
+        n0 = _c(patches["nrm"], np.float64).reshape(n, 3)
+        m0 = _c(patches["mask"], np.uint64).reshape(n, self.words)
+        dev = torch.device(f"cuda:{self.device}")
+        st = self._side_stream()
+        sh = st.cuda_stream
+        tick = timer if timer is not None else (lambda phase, k: None)
+        H, W = self.H, self.W
+        with torch.cuda.stream(st):
+            c, nrm, ref = (torch.from_numpy(x).to(dev) for x in (c0, n0, ref0))
+            mask = torch.from_numpy(m0.view(np.int64)).to(dev)
+            z = torch.empty((nv, H, W), dtype=torch.float64, device=dev)
+            idm = torch.empty((nv, H, W), dtype=torch.int32, device=dev)
+            cons = torch.empty((nv, H, W), dtype=torch.uint8, device=dev)
+            viol = torch.empty((nv, H, W), dtype=torch.uint8, device=dev)
+            tick("splat", 0)
+            self.wdepth_splat_device(c, nrm, ref, mask, radius, slope, v0, nv, z, idm, stream=sh)
+            tick("consist", 0)
+            self.wdepth_consist_device(z, v0, nv, rel_tol, cons, viol, stream=sh)
+            tick("select", 0)
+            drawn = idm >= 0
+            row = idm.clamp(min=0).long()
+            if n:
+                owner = ref[row.reshape(-1)].reshape(nv, H, W)
+                normal = torch.where(drawn.unsqueeze(-1), nrm[row.reshape(-1)].reshape(nv, H, W, 3),
+                                     torch.full((), float("nan"), dtype=torch.float64, device=dev))
+            else:
+                owner = torch.full((nv, H, W), -1, dtype=torch.int32, device=dev)
+                normal = torch.full((nv, H, W, 3), float("nan"), dtype=torch.float64, device=dev)
+            here = torch.arange(v0, v0 + nv, dtype=torch.int32, device=dev).reshape(nv, 1, 1)
+            sel = drawn & (owner == here) & (cons >= int(min_consistent)) & (viol <= int(max_violations))
+            at = sel.nonzero()                                   # (view of the range, row, column), in the maps' order
+            pix = torch.stack([at[:, 0] + v0, at[:, 2], at[:, 1]], 1).to(torch.int32).contiguous()
+            m = int(pix.shape[0])
+            xyz = torch.empty((m, 3), dtype=torch.float64, device=dev)
+            rgb = torch.empty((m, 3), dtype=torch.uint8, device=dev)
+            tick("points", 0)
+            self.wdepth_points_device(pix, z, v0, nv, xyz, rgb, stream=sh)
+            normals = normal[at[:, 0], at[:, 1], at[:, 2]]
+            tick("end", 0)
+            out = {"z": z.cpu().numpy(), "id": idm.cpu().numpy(), "cons": cons.cpu().numpy(),
+                   "viol": viol.cpu().numpy(), "normal": normal.cpu().numpy(), "points": xyz.cpu().numpy(),
+                   "normals": normals.cpu().numpy().reshape(m, 3), "colors": rgb.cpu().numpy(),
+                   "pix": pix.cpu().numpy()}
+        st.synchronize()
+        return out
 
     def pack_accepted(self, offset, count, mask, vlb, out, stream=None, c=None):
         """mvs_pack_accepted: the accepted candidates (count >= vlb) of a scored

@@ -223,6 +223,39 @@ struct WcolArgs {
     int32_t* nviews;         // n
 };
 
+// The depth maps of a warped patch set (mvs_depth_warp.hip; device pointers).
+// The maps cover the views v0 .. v0 + nv - 1, laid out [v - v0][y][x], and
+// belong to the caller.  The splat: zmap holds the bit patterns of positive
+// binary64 depths (+inf = empty), idmap the patch index (-1 = empty).
+struct WdepthArgs {
+    int64_t n;
+    const double* c;        // n*3
+    const double* nrm;      // n*3
+    const int32_t* ref;     // n; outside 0..V-1 = a dead row
+    const uint64_t* mask;   // n*words
+    int radius, v0, nv;
+    double slope;
+    uint64_t* zmap;         // nv*H*W
+    int32_t* idmap;         // nv*H*W
+};
+// The cross-view consistency count of a zmap as given.
+struct WconsArgs {
+    const double* zmap;     // nv*H*W
+    int v0, nv;
+    double rel_tol;
+    uint8_t* cons;          // nv*H*W
+    uint8_t* viol;          // nv*H*W (may be null)
+};
+// World points and colours of m listed pixels (view, x, y).
+struct WpointsArgs {
+    int64_t m;
+    const int32_t* pix;     // m*3
+    const double* zmap;     // nv*H*W
+    int v0, nv;
+    double* xyz;            // m*3
+    uint8_t* rgb;           // m*3
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -426,6 +459,11 @@ int mvs_launch_wfilt_support(const SceneDev* sc, const WsupArgs* a, hipStream_t 
 // k_wpatch_color
 int mvs_launch_wseed_match(const SceneDev* sc, const WseedArgs* a, hipStream_t s);
 int mvs_launch_wpatch_color(const SceneDev* sc, const WcolArgs* a, hipStream_t s);
+// the depth maps (mvs_depth_warp.hip): splat = k_wdepth_fill, k_wdepth_splat depth
+// pass and index pass; consist = k_wdepth_consist; points = k_wdepth_points
+int mvs_launch_wdepth_splat(const SceneDev* sc, const WdepthArgs* a, hipStream_t s);
+int mvs_launch_wdepth_consist(const SceneDev* sc, const WconsArgs* a, hipStream_t s);
+int mvs_launch_wdepth_points(const SceneDev* sc, const WpointsArgs* a, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

@@ -1,6 +1,7 @@
 // The warped family's C-ABI of libmvs_amd.so: the plane-warped photo test,
 // the refinement level and its view lists, the warped expansion's primitives,
-// the visibility-consistency filter and the neighbour-support test.
+// the visibility-consistency filter, the neighbour-support test, the seeds and
+// colours, and the depth maps.
 #include <cmath>
 
 #include "mvs_host.h"
@@ -818,6 +819,186 @@ int mvs_wpatch_color(mvs_ctx* ctx, int64_t n, const double* c, const int32_t* re
         const auto d_nviews = st.out(nviews, n);
         st.upload();
         wcol_launch(ctx, n, d_c, d_ref, d_mask, d_color, d_nviews, s);
+        st.finish();
+        return 0;
+    });
+}
+
+// ---- depth maps of a warped patch set (mvs_depth_warp.hip) ----
+
+static int need_views(mvs_ctx* ctx, const char* who, int v0, int nv) {
+    return v0 < 0 || nv < 1 || (int64_t)v0 + nv > ctx->V
+               ? bad_arg(ctx, who, "the view range v0 .. v0 + nv - 1 must lie inside 0..V-1, nv >= 1")
+               : 0;
+}
+
+static int wsplat_check(mvs_ctx* ctx, int64_t n, int radius, double slope, int v0, int nv, bool maps_ok,
+                        bool rows_ok) {
+    const char* who = "mvs_wdepth_splat";
+    if (int rc = need_nonneg(ctx, who, "n", n)) return rc;
+    if (n >= ((int64_t)1 << 31)) return bad_arg(ctx, who, "n must be below 2^31");
+    if (radius < 0 || radius > 3) return bad_arg(ctx, who, "radius must be in 0..3");
+    if (!(slope > 0.0 && slope < HUGE_VAL)) return bad_arg(ctx, who, "slope must be finite and > 0");
+    if (int rc = need_views(ctx, who, v0, nv)) return rc;
+    if (!maps_ok || (n > 0 && !rows_ok)) return bad_arg(ctx, who, "null pointer");
+    return 0;
+}
+
+static void wsplat_launch(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                          const uint64_t* d_mask, int radius, double slope, int v0, int nv, double* d_zmap,
+                          int32_t* d_idmap, hipStream_t s) {
+    WdepthArgs a{};
+    a.n = n;
+    a.c = d_c;
+    a.nrm = d_nrm;
+    a.ref = d_ref;
+    a.mask = d_mask;
+    a.radius = radius;
+    a.v0 = v0;
+    a.nv = nv;
+    a.slope = slope;
+    a.zmap = (uint64_t*)d_zmap;
+    a.idmap = d_idmap;
+    if (mvs_launch_wdepth_splat(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wdepth_splat launch failed"};
+}
+
+int mvs_wdepth_splat_device(mvs_ctx* ctx, int64_t n, const double* d_c, const double* d_nrm, const int32_t* d_ref,
+                            const uint64_t* d_mask, int radius, double slope, int v0, int nv, double* d_zmap,
+                            int32_t* d_idmap, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wsplat_check(ctx, n, radius, slope, v0, nv, d_zmap && d_idmap, d_c && d_nrm && d_ref && d_mask))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wsplat_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, radius, slope, v0, nv, d_zmap, d_idmap, s);
+        return 0;
+    });
+}
+
+int mvs_wdepth_splat(mvs_ctx* ctx, int64_t n, const double* c, const double* nrm, const int32_t* ref,
+                     const uint64_t* mask, int radius, double slope, int v0, int nv, double* zmap, int32_t* idmap) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wsplat_check(ctx, n, radius, slope, v0, nv, zmap && idmap, c && nrm && ref && mask)) return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const int64_t pixels = (int64_t)nv * ctx->H * ctx->W;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_c = st.in(c, n * 3);
+        const auto d_nrm = st.in(nrm, n * 3);
+        const auto d_mask = st.in(mask, n * ctx->words());
+        const auto d_ref = st.in(ref, n);
+        const auto d_zmap = st.out(zmap, pixels);
+        const auto d_idmap = st.out(idmap, pixels);
+        st.upload();
+        wsplat_launch(ctx, n, d_c, d_nrm, d_ref, d_mask, radius, slope, v0, nv, d_zmap, d_idmap, s);
+        st.finish();
+        return 0;
+    });
+}
+
+static int wcons_check(mvs_ctx* ctx, int v0, int nv, double rel_tol, bool ptrs_ok) {
+    const char* who = "mvs_wdepth_consist";
+    if (!(rel_tol >= 0.0 && rel_tol < HUGE_VAL)) return bad_arg(ctx, who, "rel_tol must be finite and >= 0");
+    if (int rc = need_views(ctx, who, v0, nv)) return rc;
+    if (!ptrs_ok) return bad_arg(ctx, who, "null pointer (only viol may be NULL)");
+    return 0;
+}
+
+static void wcons_launch(mvs_ctx* ctx, const double* d_zmap, int v0, int nv, double rel_tol, uint8_t* d_cons,
+                         uint8_t* d_viol, hipStream_t s) {
+    WconsArgs a{};
+    a.zmap = d_zmap;
+    a.v0 = v0;
+    a.nv = nv;
+    a.rel_tol = rel_tol;
+    a.cons = d_cons;
+    a.viol = d_viol;
+    if (mvs_launch_wdepth_consist(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wdepth_consist launch failed"};
+}
+
+int mvs_wdepth_consist_device(mvs_ctx* ctx, const double* d_zmap, int v0, int nv, double rel_tol, uint8_t* d_cons,
+                              uint8_t* d_viol, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wcons_check(ctx, v0, nv, rel_tol, d_zmap && d_cons)) return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wcons_launch(ctx, d_zmap, v0, nv, rel_tol, d_cons, d_viol, s);
+        return 0;
+    });
+}
+
+int mvs_wdepth_consist(mvs_ctx* ctx, const double* zmap, int v0, int nv, double rel_tol, uint8_t* cons,
+                       uint8_t* viol) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wcons_check(ctx, v0, nv, rel_tol, zmap && cons)) return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const int64_t pixels = (int64_t)nv * ctx->H * ctx->W;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_zmap = st.in(zmap, pixels);
+        const auto d_cons = st.out(cons, pixels);
+        const auto d_viol = st.out(viol, pixels);
+        st.upload();
+        wcons_launch(ctx, d_zmap, v0, nv, rel_tol, d_cons, d_viol, s);
+        st.finish();
+        return 0;
+    });
+}
+
+static int wpoints_check(mvs_ctx* ctx, int64_t m, int v0, int nv, bool map_ok, bool rows_ok) {
+    const char* who = "mvs_wdepth_points";
+    if (int rc = need_nonneg(ctx, who, "m", m)) return rc;
+    if (m >= ((int64_t)1 << 31)) return bad_arg(ctx, who, "m must be below 2^31");
+    if (int rc = need_views(ctx, who, v0, nv)) return rc;
+    if (!map_ok || (m > 0 && !rows_ok)) return bad_arg(ctx, who, "null pointer");
+    return 0;
+}
+
+static void wpoints_launch(mvs_ctx* ctx, int64_t m, const int32_t* d_pix, const double* d_zmap, int v0, int nv,
+                           double* d_xyz, uint8_t* d_rgb, hipStream_t s) {
+    WpointsArgs a{};
+    a.m = m;
+    a.pix = d_pix;
+    a.zmap = d_zmap;
+    a.v0 = v0;
+    a.nv = nv;
+    a.xyz = d_xyz;
+    a.rgb = d_rgb;
+    if (mvs_launch_wdepth_points(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wdepth_points launch failed"};
+}
+
+int mvs_wdepth_points_device(mvs_ctx* ctx, int64_t m, const int32_t* d_pix, const double* d_zmap, int v0, int nv,
+                             double* d_xyz, uint8_t* d_rgb, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wpoints_check(ctx, m, v0, nv, d_zmap != nullptr, d_pix && d_xyz && d_rgb)) return rc;
+    if (m == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wpoints_launch(ctx, m, d_pix, d_zmap, v0, nv, d_xyz, d_rgb, s);
+        return 0;
+    });
+}
+
+int mvs_wdepth_points(mvs_ctx* ctx, int64_t m, const int32_t* pix, const double* zmap, int v0, int nv, double* xyz,
+                      uint8_t* rgb) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    if (int rc = wpoints_check(ctx, m, v0, nv, zmap != nullptr, pix && xyz && rgb)) return rc;
+    if (m == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        for (int64_t k = 0; k < m; ++k) {
+            const int32_t* q = pix + 3 * k;
+            if (q[0] < v0 || q[0] >= v0 + nv || q[1] < 0 || q[1] >= ctx->W || q[2] < 0 || q[2] >= ctx->H)
+                throw Fail{MVS_E_ARG, "mvs_wdepth_points: listed pixel outside the view range or the image"};
+        }
+        hipStream_t s = ctx->stream;
+        const int64_t pixels = (int64_t)nv * ctx->H * ctx->W;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_zmap = st.in(zmap, pixels);
+        const auto d_xyz = st.out(xyz, m * 3);
+        const auto d_pix = st.in(pix, m * 3);
+        const auto d_rgb = st.out(rgb, m * 3);
+        st.upload();
+        wpoints_launch(ctx, m, d_pix, d_zmap, v0, nv, d_xyz, d_rgb, s);
         st.finish();
         return 0;
     });

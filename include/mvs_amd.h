@@ -612,6 +612,93 @@ int mvs_wdepth_points_device(mvs_ctx* ctx, int64_t m, const int32_t* d_pix, cons
                              int nv, double* d_xyz, uint8_t* d_rgb, void* stream);
 int mvs_wdepth_points(mvs_ctx* ctx, int64_t m, const int32_t* pix, const double* zmap, int v0, int nv,
                       double* xyz, uint8_t* rgb);
+/* ---- Per-pixel plane propagation on depth and normal maps ----
+ * (no reference counterpart).  One sweep of a PatchMatch-style densification of
+ * the maps that mvs_wdepth_splat draws: every pixel scores its own plane, the
+ * planes of four neighbours extended to it and a small depth x normal grid
+ * around its own plane against the plane-warped photo test, and takes the best.
+ * A sweep is Jacobi style: it reads one set of maps and writes another, so the
+ * result does not depend on any order of execution.  Cameras, rays, gray
+ * values, the window, the bilinear form and the ncc are mvs_score_warped's;
+ * the ray d_q of the integer pixel q and the centre O_v are the depth maps'
+ * above (camera z of d is 1, so a map value is the camera depth).
+ * Inputs, over the view range v0 .. v0 + nv - 1, laid out [v - v0][y][x]:
+ * zmap binary64 (nv H W; a depth is a finite value > 0, anything else is
+ * empty) and nmap binary64 (nv H W 3; the plane normal towards the cameras,
+ * NOT normalised or checked; a nan component makes the pixel empty).  lists is
+ * a HOST array int32 (nv, tv), tv in 1..32: row k is the list of views that the
+ * pixels of view v0 + k are matched against -- absolute view numbers in
+ * 0..V-1 (they need not lie in the range), distinct, none equal to the row's
+ * own view, -1 only at the end; |T| = the number of entries >= 0.  Both calls
+ * validate the lists.  Scalars: wid in 1..5, min_cos in [0, 1), min_ncc not
+ * nan, top_k in 1..tv, step in 1..64, kd in 0..3, ka in 0..2, astep >= 0 in
+ * radians, depth_px finite and > 0, step_scale > 0, ka astep step_scale <= 1.2.
+ * Outputs, each written whole, none overlapping an input or another output:
+ * z_out (nv H W), n_out (nv H W 3), score (nv H W) binary64, best int32
+ * (nv H W), and scores binary64 (nv H W HY; may be NULL).
+ * Per pixel q of view v of the range:
+ *   1. Pixel test.  The window [q.x-wid, q.x+wid] x [q.y-wid, q.y+wid] must lie
+ *      inside the image and its gray values a must not be constant (N sum a^2 -
+ *      (sum a)^2 > 0); otherwise the pixel comes out empty.  The window is the
+ *      integer pixels around q: nothing is projected into v.
+ *   2. Hypotheses, HY = 5 + (2 kd + 1)(2 ka + 1)^2 planes (z_h, n_h) through
+ *      X_h = O_v + z_h d_q (each component one product and one sum):
+ *      h = 0 is the pixel's own plane (z, n); it exists when the pixel is not
+ *      empty.
+ *      h = 1..4 are the planes of the pixels (q.x-step, q.y), (q.x+step, q.y),
+ *      (q.x, q.y-step), (q.x, q.y+step) extended to q: with the neighbour's
+ *      (z', n') and ray d', z_h = (z' (n'.d')) / (n'.d_q), the dot products
+ *      left to right and unfused, n_h = n' bit for bit.  The hypothesis does
+ *      not exist when the neighbour lies outside the image or is empty, when
+ *      the denominator is 0, or when z_h is not finite and > 0.  A neighbour
+ *      within wid of the border is a valid source.
+ *      h = 5 + ((k + kd) A + (j + ka)) A + (i + ka), A = 2 ka + 1, k = -kd..kd,
+ *      i, j = -ka..ka is the refinement grid around the own plane; it exists
+ *      only when h = 0 does.  dz = (depth_px z) / ((fx_v + fy_v) / 2),
+ *      z_h = z + ((double)k dz) step_scale, and n_ij is exactly step 2 of
+ *      mvs_refine_warped with nrm = n (the tangents from the host's libm,
+ *      n_00 = n as given).  The grid's centre entry (k = i = j = 0) is h = 0
+ *      again: it is never scored and its scores entry is nan.
+ *   3. Score of an existing hypothesis.  It is invalid unless n_h.(O_v - X_h) >
+ *      min_cos |O_v - X_h|.  For each list view u, in list order, ncc_u comes
+ *      from steps 3-6 of mvs_score_warped with (n_h, X_h): the facing test,
+ *      every window sample with positive depth and inside u, a warped window
+ *      that is not constant; ncc_u is nan when any of these fails.  A view
+ *      passes when ncc_u > min_ncc, and the hypothesis is valid when at least
+ *      top_k views pass.  score_h = (the sum of the top_k largest passing ncc,
+ *      added in descending order, equal values in list order) / top_k.  Every
+ *      hypothesis thus averages the same number of terms, and an occluded list
+ *      view costs nothing as long as top_k others see the plane.
+ *   4. Choice, the refinement's rule.  The own plane is kept unless another
+ *      valid hypothesis scores strictly higher; among the others the highest
+ *      score wins, ties go to the lowest h.  best = the chosen h, score = its
+ *      score (the same bits as scores[.. best]), z_out and n_out = its (z_h,
+ *      n_h) -- for h = 0 the inputs bit for bit.  With no valid hypothesis or
+ *      a failed pixel test: best -1, z_out +inf, n_out and score nan, every
+ *      scores entry nan.  So a sweep is also a per-pixel photo check: a depth
+ *      that no top_k views confirm is removed, and a pixel within wid of the
+ *      border holds nothing afterwards.
+ * Binary64 throughout; results are deterministic.  Geometry outside the sample
+ * loop is left to right and unfused; the sample positions use k_refine_warp's
+ * homogeneous form.  nv H W = 0 returns MVS_OK and launches nothing.
+ * MVS_E_ARG (message in mvs_last_error) for a scalar out of range, a NULL
+ * required pointer, a bad list, a view range outside 0..V-1 and overlapping
+ * arrays.  The call reads the scene and its arguments only (k_wprop_sweep, one
+ * launch per view, the view's list in the kernel arguments): no scorer
+ * scratch, no counter sets, no atomics, no context state.  It may be
+ * interleaved with every other call.  Device pointers, stream-ordered (NULL =
+ * the context's stream). */
+int mvs_wprop_sweep_device(mvs_ctx* ctx, int v0, int nv, const double* d_zmap, const double* d_nmap,
+                           const int32_t* lists, int tv, int wid, double min_cos, double min_ncc, int top_k,
+                           int step, int kd, int ka, double astep, double depth_px, double step_scale,
+                           double* d_z_out, double* d_n_out, double* d_score, int32_t* d_best,
+                           double* d_scores, void* stream);
+/* Same on host pointers; synchronous, on the context's stream and the staging
+ * buffer that every host-pointer call of the context shares. */
+int mvs_wprop_sweep(mvs_ctx* ctx, int v0, int nv, const double* zmap, const double* nmap, const int32_t* lists,
+                    int tv, int wid, double min_cos, double min_ncc, int top_k, int step, int kd, int ka,
+                    double astep, double depth_px, double step_scale, double* z_out, double* n_out,
+                    double* score, int32_t* best, double* scores);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

@@ -24,7 +24,10 @@ warped_patches.ply, an oriented point cloud; it needs neither SfM nor -seeds:
 
 With -depth_maps DIR [-depth_radius R] it also renders per-view depth and normal
 maps from the patches (DIR/depth_%04d.npy, DIR/normal_%04d.npy) and writes the
-dense cloud fused from them as warped_dense.ply.
+dense cloud fused from them as warped_dense.ply.  With -densify N on top of that
+the maps are first densified by N sweeps of per-pixel plane propagation
+(MvsContext.densify_depth's default schedule, at most 12): the densified maps are
+written instead, with DIR/score_%04d.npy, and warped_dense.ply is fused from them.
 """
 import importlib
 import os
@@ -55,7 +58,7 @@ def main(args, threshold=0.01, MIN_REPROJECTION_ERROR=0.3):
         # with normals (MVS2.DensePointsWarped); single process
         mvs.DensePointsWarped(imgs, args, rounds=args.warped_rounds, iterations=args.warped_iterations,
                               epi_px=args.epi_px, expand={"cell_size": args.cell_size},
-                              depth_maps=args.depth_maps, depth_radius=args.depth_radius)
+                              depth_maps=args.depth_maps, depth_radius=args.depth_radius, densify=getattr(args, "densify", 0))
         return
     if getattr(args, "seeds", None):
         global_set = mvs.SeedSet.load(args.seeds)
@@ -110,6 +113,9 @@ if __name__ == "__main__":
                              "cloud fused from them goes to warped_dense.ply")
     parser.add_argument("-depth_radius", dest="depth_radius", default=1, type=int,
                         help="--warped -depth_maps: the splat's footprint radius in pixels, 0..3")
+    parser.add_argument("-densify", dest="densify", default=0, type=int,
+                        help="--warped -depth_maps: densify the maps by this many sweeps of per-pixel plane "
+                             "propagation (the default schedule: 1..12, anything above is refused; 0: none); needs -depth_maps")
     args = parser.parse_args()
     try:
         main(args)

@@ -165,22 +165,32 @@ def depth_maps_warped(ctx, patches, **kw):
     return ctx.depth_maps(patches, **kw)
 
 
+def densify_depth_warped(ctx, maps, **kw):
+    """The maps of depth_maps_warped densified by per-pixel plane propagation
+    and fused again (no reference counterpart; see MvsContext.densify_depth,
+    which takes the keywords): `maps` needs z and normal."""
+    return ctx.densify_depth(maps, **kw)
+
+
 def write_depth_maps(maps, directory, first_view=0, dense_path="warped_dense"):
-    """The files of a depth_maps_warped result: directory/depth_%04d.npy (H,W)
-    float32, nan for empty pixels, and directory/normal_%04d.npy (H,W,3)
-    float32 per view, and the fused cloud as dense_path + '.ply'
-    (export2ply_oriented)."""
+    """The files of a depth_maps_warped or densify_depth_warped result:
+    directory/depth_%04d.npy (H,W) float32, nan for empty pixels, and
+    directory/normal_%04d.npy (H,W,3) float32 per view, score_%04d.npy (H,W)
+    float32 where the result has a score (the densified maps), and the fused
+    cloud as dense_path + '.ply' (export2ply_oriented)."""
     os.makedirs(directory, exist_ok=True)
     for k in range(len(maps["z"])):
         z = np.where(np.isfinite(maps["z"][k]), maps["z"][k], np.nan).astype(np.float32)
         np.save(os.path.join(directory, "depth_%04d.npy" % (first_view + k)), z)
         np.save(os.path.join(directory, "normal_%04d.npy" % (first_view + k)), maps["normal"][k].astype(np.float32))
+        if "score" in maps:
+            np.save(os.path.join(directory, "score_%04d.npy" % (first_view + k)), maps["score"][k].astype(np.float32))
     export2ply_oriented(maps["points"], maps["normals"], maps["colors"], path=dense_path)
 
 
 def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1e-4, neighbours=4, min_axis_cos=0.5,
                       feats=None, pairs=None, path="warped_patches", device=None, depth_maps=None, depth_radius=1,
-                      dense_path="warped_dense", **kw):
+                      dense_path="warped_dense", densify=0, **kw):
     """An oriented, coloured point cloud from calibrated images alone (no
     reference counterpart; PMVS's match -> expand -> filter on the warped
     pipeline, without SfM tracks):
@@ -203,13 +213,23 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
     write_depth_maps -- depth_%04d.npy and normal_%04d.npy per view into the
     directory and the fused cloud as dense_path + '.ply'; the count line and
     the counts gain "dense", the number of fused points, and the returned dict
-    gains "maps".
+    gains "maps".  densify = N > 0 (default 0: nothing changes): the first N sweeps
+    of MvsContext.densify_depth's default schedule run on those maps; the
+    densified maps are written instead, with score_%04d.npy per view, the dense
+    cloud is fused from them, and the count line and the counts gain
+    "densified", the pixels that hold a depth afterwards.  N above the schedule's
+    12 sweeps, or N > 0 without depth_maps, raises RuntimeError.
 
     Returns a dict: points, normals, colors (n,3), nviews, patches (the final
     set as reconstruct_warped returns it) and counts (features, pairs, tests,
     candidates, winners0, patches per iteration); the counts are also left in
     MVS2.last_stats."""
     t0 = time.time()
+    densify = int(densify)
+    if densify < 0 or densify > len(_lib.MvsContext.DENSIFY_SCHEDULE):
+        raise RuntimeError(f"densify must be in 0..{len(_lib.MvsContext.DENSIFY_SCHEDULE)} (the sweeps of the default schedule)")
+    if densify > 0 and depth_maps is None:
+        raise RuntimeError("densify needs depth_maps (a directory for the maps it densifies)")
     par_K, par_r, par_t = read_pars(args)
     ctx = scene_context(imgs, par_K, par_r, par_t, device)
     expand = dict(kw.pop("expand", None) or {})
@@ -229,11 +249,15 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
     maps = None
     if depth_maps is not None:
         maps = ctx.depth_maps(ps, radius=depth_radius)
+        if densify > 0:
+            maps = ctx.densify_depth(maps, schedule=ctx.DENSIFY_SCHEDULE[:densify])
+            counts["densified"] = int(np.isfinite(maps["z"]).sum())
         write_depth_maps(maps, depth_maps, dense_path=dense_path)
         counts["dense"] = len(maps["points"])
     counts["seconds"] = time.time() - t0
     print("warped: features {features} pairs {pairs} candidates {candidates} round-0 winners {winners0} "
-          "patches per iteration {patches}".format(**counts) + (" dense {dense}".format(**counts) if maps else ""))
+          "patches per iteration {patches}".format(**counts) + (" dense {dense}".format(**counts) if maps else "")
+          + (" densified {densified}".format(**counts) if "densified" in counts else ""))
     last_stats.clear()
     last_stats.update(counts)
     out = {"points": ps["c"], "normals": ps["nrm"], "colors": colors, "nviews": nviews, "patches": ps,

@@ -87,6 +87,14 @@ SIGNATURES = [
     ("mvs_wdepth_points_device", ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_int, _vp, _vp,
                                                 _vp]),
     ("mvs_wdepth_points", ctypes.c_int, [_vp, ctypes.c_int64, _i32p, _dp, ctypes.c_int, ctypes.c_int, _dp, _u8p]),
+    ("mvs_wprop_sweep_device", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _vp, _vp, _i32p, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                              ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("mvs_wprop_sweep", ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _i32p, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, _dp, _dp,
+                                       _dp, _i32p, _dp]),
     ("mvs_pack_accepted", ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int,
                                          ctypes.c_int64, _vp, _vp]),
     ("mvs_set_scorer_grid", ctypes.c_int, [_vp, ctypes.c_int]),
@@ -265,6 +273,21 @@ def seed_view_pairs(Rp, neighbours=4, min_axis_cos=0.5):
         keep.sort(key=lambda dv: (-dv[0], dv[1]))
         out += [(r, v) for _, v in keep[:max(int(neighbours), 0)]]
     return np.array(out, np.int32).reshape(-1, 2)
+
+
+def wprop_view_lists(Rp, tv=4, min_axis_cos=0.5, v0=0, nv=None):
+    """The view lists of the propagation sweep for the views v0 .. v0 + nv - 1
+    -> (nv, tv) int32: the rows of seed_view_pairs(Rp, tv, min_axis_cos) grouped
+    by their first view, in that order, padded with -1."""
+    Rp = np.asarray(Rp, np.float64).reshape(-1, 3, 3)
+    nv = len(Rp) - v0 if nv is None else int(nv)
+    out = np.full((nv, int(tv)), -1, np.int32)
+    fill = [0] * nv
+    for r, v in seed_view_pairs(Rp, int(tv), min_axis_cos).tolist():
+        if v0 <= r < v0 + nv:
+            out[r - v0, fill[r - v0]] = v
+            fill[r - v0] += 1
+    return out
 
 
 # live contexts: a retiring caller stream is announced to each of them
@@ -1846,6 +1869,162 @@ class MvsContext:
                    "viol": viol.cpu().numpy(), "normal": normal.cpu().numpy(), "points": xyz.cpu().numpy(),
                    "normals": normals.cpu().numpy().reshape(m, 3), "colors": rgb.cpu().numpy(),
                    "pix": pix.cpu().numpy()}
+        st.synchronize()
+        return out
+
+    # the default schedule of densify_depth: (step, kd, ka, step_scale) per sweep
+    DENSIFY_SCHEDULE = tuple((st, 1, 1, 1.0 if k < 4 else 0.5)
+                             for k, st in enumerate((1, 3, 1, 5, 1, 3, 1, 1, 1, 1, 1, 1)))
+    DENSIFY_ASTEP = math.radians(8)
+    DENSIFY_DEPTH_PX = 1.0
+
+    @staticmethod
+    def wprop_hypotheses(kd, ka):
+        """HY = 5 + (2 kd + 1)(2 ka + 1)^2: the hypotheses of a pixel in one sweep."""
+        return 5 + (2 * int(kd) + 1) * (2 * int(ka) + 1) ** 2
+
+    def wprop_view_lists(self, tv=4, min_axis_cos=0.5, views=None):
+        """The view lists a sweep is fed -> (nv, tv) int32: the rows of
+        seed_view_pairs(rproj(), tv, min_axis_cos) grouped by their first view
+        (in that order) and padded with -1: one rule for neighbour views in the
+        whole warped family.  views: None (every view) or (v0, nv)."""
+        v0, nv = self._view_range(views)
+        return wprop_view_lists(self.rproj(), tv, min_axis_cos, v0, nv)
+
+    def _wprop_lists(self, lists, nv):
+        lists = _c(lists, np.int32)
+        if lists.ndim != 2 or lists.shape[0] != nv or not 1 <= lists.shape[1] <= 32:
+            raise RuntimeError(f"wprop_sweep: lists must be ({nv}, tv) with tv in 1..32")
+        return lists
+
+    def wprop_sweep_device(self, zmap, nmap, lists, v0, nv, z_out, n_out, score, best, scores=None, wid=5,
+                           min_cos=0.3, min_ncc=0.7, top_k=2, step=1, kd=1, ka=1, astep=math.radians(8),
+                           depth_px=1.0, step_scale=1.0, stream=None):
+        """mvs_wprop_sweep_device on torch device tensors (contiguous: zmap,
+        z_out, score float64 (nv,H,W), nmap, n_out float64 (nv,H,W,3), best int32
+        (nv,H,W), scores float64 (nv,H,W,HY) or None; every output written whole);
+        lists is a host int32 array (nv, tv).  Stream-ordered."""
+        nv = int(nv)
+        lists = self._wprop_lists(lists, nv)
+        maps = (nv, self.H, self.W)
+        hy = self.wprop_hypotheses(kd, ka)
+        for name, x, size, shape in [("zmap", zmap, 8, maps), ("nmap", nmap, 8, maps + (3,)), ("z_out", z_out, 8, maps),
+                                     ("n_out", n_out, 8, maps + (3,)), ("score", score, 8, maps),
+                                     ("best", best, 4, maps), ("scores", scores, 8, maps + (hy,))]:
+            if x is None and name == "scores":
+                continue
+            if x.dtype.itemsize != size or tuple(x.shape) != shape or not x.is_contiguous():
+                raise RuntimeError(f"wprop_sweep_device: {name} must be contiguous, {size}-byte elements, {shape}")
+        rc = load().mvs_wprop_sweep_device(self._h, int(v0), nv, zmap.data_ptr(), nmap.data_ptr(), _p(lists, _i32p),
+                                           lists.shape[1], int(wid), float(min_cos), float(min_ncc), int(top_k),
+                                           int(step), int(kd), int(ka), float(astep), float(depth_px),
+                                           float(step_scale), z_out.data_ptr(), n_out.data_ptr(), score.data_ptr(),
+                                           best.data_ptr(), scores.data_ptr() if scores is not None else None,
+                                           self._stream_handle(stream))
+        check(rc, self._h, "mvs_wprop_sweep_device")
+
+    def wprop_sweep(self, zmap, nmap, lists, views=None, wid=5, min_cos=0.3, min_ncc=0.7, top_k=2, step=1, kd=1, ka=1,
+                    astep=math.radians(8), depth_px=1.0, step_scale=1.0, want_scores=False):
+        """One propagation sweep on numpy maps (mvs_wprop_sweep, host pointers)
+        -> dict z (nv,H,W), normal (nv,H,W,3), score, best int32 and, with
+        want_scores, scores (nv,H,W,HY)."""
+        v0, nv = self._view_range(views)
+        lists = self._wprop_lists(lists, nv)
+        maps = (nv, self.H, self.W)
+        zmap = _c(zmap, np.float64).reshape(maps)
+        nmap = _c(nmap, np.float64).reshape(maps + (3,))
+        z = np.empty(maps)
+        n = np.empty(maps + (3,))
+        score = np.empty(maps)
+        best = np.empty(maps, np.int32)
+        scores = np.empty(maps + (self.wprop_hypotheses(kd, ka),)) if want_scores else None
+        rc = load().mvs_wprop_sweep(self._h, v0, nv, _p(zmap, _dp), _p(nmap, _dp), _p(lists, _i32p), lists.shape[1],
+                                    int(wid), float(min_cos), float(min_ncc), int(top_k), int(step), int(kd), int(ka),
+                                    float(astep), float(depth_px), float(step_scale), _p(z, _dp), _p(n, _dp),
+                                    _p(score, _dp), _p(best, _i32p), _p(scores, _dp) if want_scores else None)
+        check(rc, self._h, "mvs_wprop_sweep")
+        out = {"z": z, "normal": n, "score": score, "best": best}
+        if want_scores:
+            out["scores"] = scores
+        return out
+
+    def densify_depth(self, maps, views=None, lists=None, tv=4, wid=5, min_ncc=0.7, min_cos=0.3, top_k=2,
+                      schedule=None, rel_tol=0.01, min_consistent=2, max_violations=0, timer=None):
+        """Densify the maps depth_maps returns (`maps` needs z and normal) by
+        per-pixel plane propagation (mvs_wprop_sweep, include/mvs_amd.h) and fuse
+        them.  Two sets of device maps are ping-ponged through the sweeps of
+        `schedule`, a list of (step, kd, ka, step_scale) (default
+        DENSIFY_SCHEDULE: 12 sweeps, steps 1,3,1,5,1,3,1,1,1,1,1,1, a 3 x 3 x 3
+        grid of 1 px in depth and 8 degrees, halved after the fourth sweep);
+        lists: the (nv, tv) view lists (default wprop_view_lists(tv)).  Then
+        wdepth_consist_device counts the agreeing views and a pixel is fused
+        when it holds a depth, cons >= min_consistent and viol <=
+        max_violations.  There is no ref rule here -- a densified pixel has no
+        owner patch -- so a surface point is emitted in every view that holds
+        it; the cloud is not de-duplicated across views.  Everything runs on
+        the context's torch side stream.
+
+        Returns a dict of numpy arrays: z (nv,H,W) float64 (+inf = empty),
+        normal (nv,H,W,3) (nan where empty), score float64, best int32 (of the
+        last sweep), cons and viol uint8, the fused cloud points (m,3), normals
+        (m,3), colors (m,3) uint8, pix (m,3) int32 rows (view, x, y) in the
+        maps' order, and history (sweeps, 2) int64: per sweep the pixels that
+        hold a depth after it and the pixels whose best > 0 (gathered on the
+        device, copied once at the end).  timer: an optional callable
+        timer(phase, k) called on the chain's stream before sweep k ("sweep"),
+        before "consist", "select" and "points", and with "end" after the last."""
+        import torch
+        v0, nv = self._view_range(views)
+        H, W = self.H, self.W
+        if lists is None:
+            lists = self.wprop_view_lists(tv, views=(v0, nv))
+        lists = self._wprop_lists(lists, nv)
+        schedule = list(self.DENSIFY_SCHEDULE if schedule is None else schedule)
+        z0 = _c(maps["z"], np.float64).reshape(nv, H, W)
+        n0 = _c(maps["normal"], np.float64).reshape(nv, H, W, 3)
+        dev = torch.device(f"cuda:{self.device}")
+        st = self._side_stream()
+        sh = st.cuda_stream
+        tick = timer if timer is not None else (lambda phase, k: None)
+        with torch.cuda.stream(st):
+            z = [torch.from_numpy(z0).to(dev), torch.empty((nv, H, W), dtype=torch.float64, device=dev)]
+            nm = [torch.from_numpy(n0).to(dev), torch.empty((nv, H, W, 3), dtype=torch.float64, device=dev)]
+            score = torch.full((nv, H, W), float("nan"), dtype=torch.float64, device=dev)
+            best = torch.full((nv, H, W), -1, dtype=torch.int32, device=dev)
+            hist = torch.zeros((max(len(schedule), 1), 2), dtype=torch.int64, device=dev)
+            cur = 0
+            for k, (step, kd, ka, scale) in enumerate(schedule):
+                tick("sweep", k)
+                self.wprop_sweep_device(z[cur], nm[cur], lists, v0, nv, z[1 - cur], nm[1 - cur], score, best, None,
+                                        wid, min_cos, min_ncc, top_k, step, kd, ka, self.DENSIFY_ASTEP,
+                                        self.DENSIFY_DEPTH_PX, scale, stream=sh)
+                cur = 1 - cur
+                hist[k, 0] = (best >= 0).sum()
+                hist[k, 1] = (best > 0).sum()
+            zf, nf = z[cur], nm[cur]
+            if not schedule:   # no sweep: the maps as given
+                zf = torch.where(torch.isfinite(zf) & (zf > 0), zf, torch.full((), float("inf"), dtype=torch.float64,
+                                                                               device=dev))
+            cons = torch.empty((nv, H, W), dtype=torch.uint8, device=dev)
+            viol = torch.empty((nv, H, W), dtype=torch.uint8, device=dev)
+            tick("consist", 0)
+            self.wdepth_consist_device(zf, v0, nv, rel_tol, cons, viol, stream=sh)
+            tick("select", 0)
+            sel = torch.isfinite(zf) & (zf > 0) & (cons >= int(min_consistent)) & (viol <= int(max_violations))
+            at = sel.nonzero()                                   # (view of the range, row, column), in the maps' order
+            pix = torch.stack([at[:, 0] + v0, at[:, 2], at[:, 1]], 1).to(torch.int32).contiguous()
+            m = int(pix.shape[0])
+            xyz = torch.empty((m, 3), dtype=torch.float64, device=dev)
+            rgb = torch.empty((m, 3), dtype=torch.uint8, device=dev)
+            tick("points", 0)
+            self.wdepth_points_device(pix, zf, v0, nv, xyz, rgb, stream=sh)
+            normals = nf[at[:, 0], at[:, 1], at[:, 2]]
+            tick("end", 0)
+            out = {"z": zf.cpu().numpy(), "normal": nf.cpu().numpy(), "score": score.cpu().numpy(),
+                   "best": best.cpu().numpy(), "cons": cons.cpu().numpy(), "viol": viol.cpu().numpy(),
+                   "points": xyz.cpu().numpy(), "normals": normals.cpu().numpy().reshape(m, 3),
+                   "colors": rgb.cpu().numpy(), "pix": pix.cpu().numpy(),
+                   "history": hist.cpu().numpy()[:len(schedule)]}
         st.synchronize()
         return out
 

@@ -27,27 +27,13 @@
 // Binary64 in the library's operation order, compiled with -ffp-contract=off.
 #include <algorithm>
 
-#include "mvs_device.h"
+#include "mvs_planes.h"
 
 namespace {
 
 constexpr uint64_t kInfBits = 0x7ff0000000000000ull;
 
 DEV bool finite(double x) { return x > -__builtin_inf() && x < __builtin_inf(); }
-
-// O = -Rp^T t, each component a left-to-right sum of three products (k_wexp_children's)
-DEV void centre(const CamDev& cv, double* O) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) O[k] = -(cv.Rp[k] * cv.t[0] + cv.Rp[3 + k] * cv.t[1] + cv.Rp[6 + k] * cv.t[2]);
-}
-
-// d = Rp^T ((qx - cx) / fx, (qy - cy) / fy, 1): the ray of the integer pixel q, camera z = 1
-DEV void pixel_ray(const CamDev& cv, int qx, int qy, double* d) {
-    const double u = ((double)qx - cv.cx) / cv.fx;
-    const double w = ((double)qy - cv.cy) / cv.fy;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) d[m] = cv.Rp[m] * u + cv.Rp[3 + m] * w + cv.Rp[6 + m];
-}
 
 __global__ __launch_bounds__(256) void k_wdepth_fill(int64_t pixels, uint64_t* zmap, int32_t* idmap) {
     const int64_t step = (int64_t)gridDim.x * blockDim.x;

@@ -256,6 +256,25 @@ struct WpointsArgs {
     uint8_t* rgb;           // m*3
 };
 
+// One view of one sweep of the per-pixel plane propagation (k_wprop_sweep,
+// mvs_prop_warp.hip; device pointers).  The maps are the view's own H*W slice;
+// the view's list travels in the arguments.
+struct WpropArgs {
+    const double* zmap;     // H*W
+    const double* nmap;     // H*W*3
+    int v;                  // the view
+    int T;                  // list entries >= 0
+    int32_t views[32];      // the list, entries T.. unused
+    int top_k, step, kd, ka;
+    double min_cos, min_ncc, depth_px, step_scale;
+    double tans[5];         // tan(i astep step_scale), i = -ka..ka, from the host's libm
+    double* z_out;          // H*W
+    double* n_out;          // H*W*3
+    double* score;          // H*W
+    int32_t* best;          // H*W
+    double* scores;         // H*W*HY (may be null), HY = 5 + (2 kd + 1)(2 ka + 1)^2
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -464,6 +483,9 @@ int mvs_launch_wpatch_color(const SceneDev* sc, const WcolArgs* a, hipStream_t s
 int mvs_launch_wdepth_splat(const SceneDev* sc, const WdepthArgs* a, hipStream_t s);
 int mvs_launch_wdepth_consist(const SceneDev* sc, const WconsArgs* a, hipStream_t s);
 int mvs_launch_wdepth_points(const SceneDev* sc, const WpointsArgs* a, hipStream_t s);
+// one view of a propagation sweep (k_wprop_sweep, mvs_prop_warp.hip): a wave per
+// 16 pixels, lane = (hypothesis, list view); wid in 1..5
+int mvs_launch_wprop_sweep(const SceneDev* sc, const WpropArgs* a, int wid, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

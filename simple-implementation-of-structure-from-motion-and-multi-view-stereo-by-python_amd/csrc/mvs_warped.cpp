@@ -1,7 +1,7 @@
 // The warped family's C-ABI of libmvs_amd.so: the plane-warped photo test,
 // the refinement level and its view lists, the warped expansion's primitives,
 // the visibility-consistency filter, the neighbour-support test, the seeds and
-// colours, and the depth maps.
+// colours, the depth maps, and the propagation sweep on them.
 #include <cmath>
 
 #include "mvs_host.h"
@@ -999,6 +999,151 @@ int mvs_wdepth_points(mvs_ctx* ctx, int64_t m, const int32_t* pix, const double*
         const auto d_rgb = st.out(rgb, m * 3);
         st.upload();
         wpoints_launch(ctx, m, d_pix, d_zmap, v0, nv, d_xyz, d_rgb, s);
+        st.finish();
+        return 0;
+    });
+}
+
+// ---- per-pixel plane propagation on the depth maps (mvs_prop_warp.hip) ----
+
+struct WpropCall {
+    int v0, nv, tv, wid, top_k, step, kd, ka;
+    double min_cos, min_ncc, astep, depth_px, step_scale;
+    const int32_t* lists;
+};
+
+// byte ranges [p, p + n) and [q, q + m) share a byte
+static bool overlaps(const void* p, size_t n, const void* q, size_t m) {
+    const char* a = (const char*)p;
+    const char* b = (const char*)q;
+    return p && q && n && m && a < b + m && b < a + n;
+}
+
+// the checks of both entry points (0, or the error's code with the message recorded)
+static int wprop_check(mvs_ctx* ctx, const WpropCall& k, const void* zmap, const void* nmap, const void* z_out,
+                       const void* n_out, const void* score, const void* best, const void* scores) {
+    const char* who = "mvs_wprop_sweep";
+    if (k.v0 < 0 || k.nv < 0 || (int64_t)k.v0 + k.nv > ctx->V)
+        return bad_arg(ctx, who, "the view range v0 .. v0 + nv - 1 must lie inside 0..V-1");
+    if (int rc = need_wid(ctx, who, k.wid)) return rc;
+    if (int rc = need_min_cos(ctx, who, k.min_cos)) return rc;
+    if (std::isnan(k.min_ncc)) return bad_arg(ctx, who, "min_ncc is nan");
+    if (k.tv < 1 || k.tv > 32) return bad_arg(ctx, who, "tv must be in 1..32");
+    if (k.top_k < 1 || k.top_k > k.tv) return bad_arg(ctx, who, "top_k must be in 1..tv");
+    if (k.step < 1 || k.step > 64) return bad_arg(ctx, who, "step must be in 1..64");
+    if (k.kd < 0 || k.kd > 3) return bad_arg(ctx, who, "kd must be in 0..3");
+    if (k.ka < 0 || k.ka > 2) return bad_arg(ctx, who, "ka must be in 0..2");
+    if (!(k.depth_px > 0.0 && k.depth_px < HUGE_VAL)) return bad_arg(ctx, who, "depth_px must be finite and > 0");
+    if (!(k.step_scale > 0.0) || !std::isfinite(k.step_scale)) return bad_arg(ctx, who, "step_scale must be > 0");
+    if (!(k.astep >= 0.0) || !((double)k.ka * k.astep * k.step_scale <= 1.2))
+        return bad_arg(ctx, who, "ka * astep * step_scale must be in [0, 1.2]");
+    if (k.nv > 0 && !k.lists) return bad_arg(ctx, who, "null pointer (lists)");
+    const int V = ctx->V;
+    for (int r = 0; r < k.nv; ++r) {
+        const int32_t* l = k.lists + (size_t)r * k.tv;
+        bool ended = false;
+        for (int j = 0; j < k.tv; ++j) {
+            if (l[j] < -1 || l[j] >= V) return bad_arg(ctx, who, "list view out of range");
+            if (l[j] < 0) { ended = true; continue; }
+            if (ended) return bad_arg(ctx, who, "list view after a -1");
+            if (l[j] == k.v0 + r) return bad_arg(ctx, who, "list view equal to the row's own view");
+            for (int i = 0; i < j; ++i)
+                if (l[i] == l[j]) return bad_arg(ctx, who, "list view repeated");
+        }
+    }
+    const size_t px = (size_t)k.nv * ctx->H * ctx->W;
+    if (px == 0) return 0;
+    if (!zmap || !nmap || !z_out || !n_out || !score || !best)
+        return bad_arg(ctx, who, "null pointer (only scores may be NULL)");
+    const int A = 2 * k.ka + 1;
+    const size_t HY = 5 + (size_t)(2 * k.kd + 1) * A * A;
+    const void* in[2] = {zmap, nmap};
+    const size_t in_b[2] = {px * 8, px * 24};
+    const void* out[5] = {z_out, n_out, score, best, scores};
+    const size_t out_b[5] = {px * 8, px * 24, px * 8, px * 4, px * HY * 8};
+    for (int o = 0; o < 5; ++o) {
+        for (int i = 0; i < 2; ++i)
+            if (overlaps(out[o], out_b[o], in[i], in_b[i])) return bad_arg(ctx, who, "an output overlaps an input");
+        for (int i = 0; i < o; ++i)
+            if (overlaps(out[o], out_b[o], out[i], out_b[i])) return bad_arg(ctx, who, "two outputs overlap");
+    }
+    return 0;
+}
+
+// one launch per view: the view's list travels in the kernel's arguments
+static void wprop_launch(mvs_ctx* ctx, const WpropCall& k, const double* d_zmap, const double* d_nmap, double* d_z_out,
+                         double* d_n_out, double* d_score, int32_t* d_best, double* d_scores, hipStream_t s) {
+    const size_t hw = (size_t)ctx->H * ctx->W;
+    const int A = 2 * k.ka + 1;
+    const size_t HY = 5 + (size_t)(2 * k.kd + 1) * A * A;
+    WpropArgs a{};
+    a.top_k = k.top_k;
+    a.step = k.step;
+    a.kd = k.kd;
+    a.ka = k.ka;
+    a.min_cos = k.min_cos;
+    a.min_ncc = k.min_ncc;
+    a.depth_px = k.depth_px;
+    a.step_scale = k.step_scale;
+    // the grid's tangents from the host's libm, as mvs_refine_warped's
+    const double alpha = k.astep * k.step_scale;
+    for (int i = -k.ka; i <= k.ka; ++i) a.tans[i + k.ka] = std::tan((double)i * alpha);
+    for (int r = 0; r < k.nv; ++r) {
+        a.v = k.v0 + r;
+        a.T = 0;
+        for (int j = 0; j < 32; ++j) {
+            a.views[j] = j < k.tv ? k.lists[(size_t)r * k.tv + j] : -1;
+            if (a.views[j] >= 0) ++a.T;
+        }
+        a.zmap = d_zmap + r * hw;
+        a.nmap = d_nmap + r * hw * 3;
+        a.z_out = d_z_out + r * hw;
+        a.n_out = d_n_out + r * hw * 3;
+        a.score = d_score + r * hw;
+        a.best = d_best + r * hw;
+        a.scores = d_scores ? d_scores + r * hw * HY : nullptr;
+        if (mvs_launch_wprop_sweep(&ctx->sc, &a, k.wid, s) != 0) throw Fail{MVS_E_HIP, "wprop_sweep launch failed"};
+    }
+}
+
+int mvs_wprop_sweep_device(mvs_ctx* ctx, int v0, int nv, const double* d_zmap, const double* d_nmap,
+                           const int32_t* lists, int tv, int wid, double min_cos, double min_ncc, int top_k, int step,
+                           int kd, int ka, double astep, double depth_px, double step_scale, double* d_z_out,
+                           double* d_n_out, double* d_score, int32_t* d_best, double* d_scores, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    const WpropCall k{v0, nv, tv, wid, top_k, step, kd, ka, min_cos, min_ncc, astep, depth_px, step_scale, lists};
+    if (int rc = wprop_check(ctx, k, d_zmap, d_nmap, d_z_out, d_n_out, d_score, d_best, d_scores)) return rc;
+    if ((int64_t)nv * ctx->H * ctx->W == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wprop_launch(ctx, k, d_zmap, d_nmap, d_z_out, d_n_out, d_score, d_best, d_scores, s);
+        return 0;
+    });
+}
+
+int mvs_wprop_sweep(mvs_ctx* ctx, int v0, int nv, const double* zmap, const double* nmap, const int32_t* lists,
+                    int tv, int wid, double min_cos, double min_ncc, int top_k, int step, int kd, int ka, double astep,
+                    double depth_px, double step_scale, double* z_out, double* n_out, double* score, int32_t* best,
+                    double* scores) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    const WpropCall k{v0, nv, tv, wid, top_k, step, kd, ka, min_cos, min_ncc, astep, depth_px, step_scale, lists};
+    if (int rc = wprop_check(ctx, k, zmap, nmap, z_out, n_out, score, best, scores)) return rc;
+    const int64_t px = (int64_t)nv * ctx->H * ctx->W;
+    if (px == 0) return MVS_OK;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        const int A = 2 * ka + 1;
+        const int64_t HY = 5 + (int64_t)(2 * kd + 1) * A * A;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_zmap = st.in(zmap, px);
+        const auto d_nmap = st.in(nmap, px * 3);
+        const auto d_zo = st.out(z_out, px);
+        const auto d_no = st.out(n_out, px * 3);
+        const auto d_sc = st.out(score, px);
+        const auto d_best = st.out(best, px);
+        const auto d_scores = st.out(scores, px * HY);
+        st.upload();
+        wprop_launch(ctx, k, d_zmap, d_nmap, d_zo, d_no, d_sc, d_best, d_scores, s);
         st.finish();
         return 0;
     });

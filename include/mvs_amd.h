@@ -699,6 +699,112 @@ int mvs_wprop_sweep(mvs_ctx* ctx, int v0, int nv, const double* zmap, const doub
                     int tv, int wid, double min_cos, double min_ncc, int top_k, int step, int kd, int ka,
                     double astep, double depth_px, double step_scale, double* z_out, double* n_out,
                     double* score, int32_t* best, double* scores);
+/* ---- A surface from the depth maps: signed-distance fusion and marching
+ * tetrahedra ----
+ * (no reference counterpart).  Every view's depth map votes into one lattice of
+ * truncated signed distances, and the surface is extracted once from it as an
+ * indexed triangle mesh: the views are merged by construction.  Cameras,
+ * "projection" and the maps' layout [v - v0][y][x] over a view range are the
+ * depth maps' above; integer coordinates are pixel centres and a depth is the
+ * camera z that the splat writes.  Binary64, products and sums left to right,
+ * unfused, so every output is defined to the bit; tests/mesh_reference.py
+ * restates both calls in Python floats.
+ *
+ * The lattice: (nx + 1)(ny + 1)(nz + 1) points, nx, ny, nz >= 1, at most 2^27
+ * of them; P(i, j, k) = origin + (i, j, k) voxel, each coordinate one product
+ * ((double)i voxel) and one sum; the point's linear index is (k (ny + 1) +
+ * j)(nx + 1) + i, which is the layout of every lattice array.  origin is a host
+ * array of 3 finite doubles, voxel is finite and > 0.
+ *
+ * mvs_wtsdf_integrate_device: trunc finite and > 0, min_weight >= 1.  For each
+ * lattice point P, D = 0, Wt = 0, cnt = 0 and three integer sums = 0, then for
+ * the views v = v0 .. v0 + nv - 1 in that order:
+ *   1. (x, y, z) = projection of P into v; skipped unless z > 0, x >= 0, y >= 0,
+ *      x + 0.5 < W and y + 0.5 < H (tested before the conversion, so nan and
+ *      huge values never reach an integer: mvs_wdepth_consist's rule); the
+ *      nearest pixel is q = (int(x + 0.5), int(y + 0.5)).
+ *   2. zu = zmap[v][q]; skipped unless zu is finite and > 0.
+ *   3. sdf = zu - z; skipped when sdf < -trunc (P is hidden behind the surface).
+ *   4. r = sdf / trunc; D += (r < 1 ? r : 1); Wt += 1.
+ *   5. When |sdf| <= trunc: the three bytes of the resident RGB image of v at q
+ *      are added to the sums and cnt += 1.
+ * tsdf[P] (binary64) = D / (double)Wt when Wt >= min_weight, else the quiet nan
+ * 0x7ff8000000000000; weight[P] (int32) = Wt; rgb[P] (3 bytes) = (2 sum + cnt) /
+ * (2 cnt) per channel in integer arithmetic, 0 when cnt = 0; cnt[P] (uint8) =
+ * min(cnt, 255).  Every element of the four arrays is written.  The call keeps
+ * no context state and reads the scene and its arguments only, so it runs on
+ * any stream beside any other call.  k_wtsdf_integrate: one thread per lattice
+ * point, a workgroup owns a brick of 16 x 4 x 4 points with i fastest (bricks
+ * past the lattice's end are cut, so no size is special); the view loop is
+ * wave-uniform with the camera in scalar registers; no atomics: the sum is in
+ * view order.
+ *
+ * mvs_wmesh_extract_device: marching tetrahedra over a lattice of values tsdf
+ * (as given; it need not come from the integration), with rgb and cnt per point.
+ * Cube (i, j, k), 0 <= i < nx .., has the linear index (k ny + j) nx + i and the
+ * corners P(i + a, j + b, k + c), a, b, c in {0, 1}.  It is cut into the six Kuhn
+ * tetrahedra, one per permutation pi of the axes (0, 1, 2) in lexicographic
+ * order (012, 021, 102, 120, 201, 210): corners c0 = (0,0,0), c1 = c0 + e_pi0,
+ * c2 = c1 + e_pi1, c3 = (1,1,1).  Neighbouring cubes agree on every face
+ * diagonal, there is no ambiguous case, and every edge of a tetrahedron runs
+ * from a lattice point p to p + delta, delta in {0,1}^3 \ {0}: p, the lower
+ * endpoint, owns the edge, whose type is delta.x + 2 delta.y + 4 delta.z - 1
+ * (0..6).
+ *   - A corner is inside when its value is < 0 (0.0 and -0.0 are outside).  A
+ *     tetrahedron draws only when its four values are finite and it has inside
+ *     and outside corners.
+ *   - One inside corner a, or one outside corner a: one triangle, the edges from
+ *     a to the other three corners in the tetrahedron's corner order.  Two
+ *     inside corners a < b, outside c < d: the triangles (ac, ad, bd) and (ac,
+ *     bd, bc).  A triangle's second and third vertex are then swapped where
+ *     needed so that (p1 - p0) x (p2 - p0) points from the inside corners to the
+ *     outside ones (a table of one bit per (tetrahedron, inside mask)).
+ *   - A vertex exists exactly for the lattice edges that some drawn triangle
+ *     uses; both tetrahedra that share an edge name the same vertex.  On the
+ *     edge from a (the owner) to b: t = f_a / (f_a - f_b), position P_a + t (P_b -
+ *     P_a) per coordinate, colour = rgb of a when t < 0.5, else of b; when that
+ *     endpoint has cnt = 0, of the other one.
+ *   - Exact zeros give triangles of zero area (all three vertices at one lattice
+ *     point); they are kept.
+ *   - Vertices are ordered by (owner's linear index, edge type), triangles by
+ *     (cube's linear index, tetrahedron, triangle); indices are int32.
+ * Sizing is mvs_wseed_match_device's: d_total[0] = the number of vertices and
+ * d_total[1] = the number of triangles (int64, device), whatever the caps; the
+ * first min(cap_v, total) vertices go to d_vert (binary64 x 3) and d_vcol (3
+ * bytes), the first min(cap_t, total) triangles to d_tri (int32 x 3; an index
+ * may name a vertex at or past cap_v), and nothing is written past a cap.
+ * cap_v = cap_t = 0 counts only (the outputs may then be NULL).  Two runs are
+ * bit-identical.  Passes: k_wmesh_mark (one thread per cube: the triangle count,
+ * and an atomic OR of the used-edge bits into the owners' masks -- an OR does
+ * not depend on the order of arrival), k_wmesh_vcount, k_wmesh_scan (exclusive
+ * offsets of the workgroups' counts), k_wmesh_vertex and k_wmesh_tri (the mark
+ * pass's arithmetic again; offsets inside a workgroup come from a scan in the
+ * workgroup).  The masks (a byte per point), the points' first vertices (int32)
+ * and the workgroups' counts live in the context's scratch, 5 bytes per point:
+ * consecutive calls on one stream follow each other in stream order, and a
+ * call on another stream waits for the previous call's work through an event
+ * (as the expansion's grids do), so calls of one context never overlap.
+ *
+ * MVS_E_ARG (message in mvs_last_error) for a scalar out of range, nan or inf
+ * (nx, ny, nz, origin, voxel, trunc, min_weight, cap_v or cap_t < 0 or >= 2^31),
+ * a NULL required pointer, a view range outside 0..V-1 or more than 2^27
+ * lattice points.  The host-pointer variants are synchronous, on the context's
+ * stream and the staging buffer that every host-pointer call of the context
+ * shares; they copy cap_v and cap_t whole entries back, of which those past the
+ * totals are unspecified.  Stream-ordered (NULL = the context's stream). */
+int mvs_wtsdf_integrate_device(mvs_ctx* ctx, const double* d_zmap, int v0, int nv, int nx, int ny, int nz,
+                               const double* origin, double voxel, double trunc, int min_weight, double* d_tsdf,
+                               int32_t* d_weight, uint8_t* d_rgb, uint8_t* d_cnt, void* stream);
+int mvs_wtsdf_integrate(mvs_ctx* ctx, const double* zmap, int v0, int nv, int nx, int ny, int nz,
+                        const double* origin, double voxel, double trunc, int min_weight, double* tsdf,
+                        int32_t* weight, uint8_t* rgb, uint8_t* cnt);
+int mvs_wmesh_extract_device(mvs_ctx* ctx, int nx, int ny, int nz, const double* origin, double voxel,
+                             const double* d_tsdf, const uint8_t* d_rgb, const uint8_t* d_cnt, int64_t cap_v,
+                             int64_t cap_t, double* d_vert, uint8_t* d_vcol, int32_t* d_tri, int64_t* d_total,
+                             void* stream);
+int mvs_wmesh_extract(mvs_ctx* ctx, int nx, int ny, int nz, const double* origin, double voxel, const double* tsdf,
+                      const uint8_t* rgb, const uint8_t* cnt, int64_t cap_v, int64_t cap_t, double* vert,
+                      uint8_t* vcol, int32_t* tri, int64_t* total);
 /* CellTable.filter_out_outlier (MVS2.py:132-158) on the host, over n accepted
  * patches in fill order (what the stage's opt-in filter mode runs between
  * the expansion and reconstruct_from_Q): patch e has cell[2e..2e+1] =

@@ -28,6 +28,9 @@ dense cloud fused from them as warped_dense.ply.  With -densify N on top of that
 the maps are first densified by N sweeps of per-pixel plane propagation
 (MvsContext.densify_depth's default schedule, at most 12): the densified maps are
 written instead, with DIR/score_%04d.npy, and warped_dense.ply is fused from them.
+With -mesh N the maps (densified when -densify is given) are also fused into a
+signed-distance lattice of N voxels along its longest side and the surface is
+written as warped_mesh.ply, a coloured triangle mesh (MvsContext.mesh_depth).
 """
 import importlib
 import os
@@ -58,7 +61,8 @@ def main(args, threshold=0.01, MIN_REPROJECTION_ERROR=0.3):
         # with normals (MVS2.DensePointsWarped); single process
         mvs.DensePointsWarped(imgs, args, rounds=args.warped_rounds, iterations=args.warped_iterations,
                               epi_px=args.epi_px, expand={"cell_size": args.cell_size},
-                              depth_maps=args.depth_maps, depth_radius=args.depth_radius, densify=getattr(args, "densify", 0))
+                              depth_maps=args.depth_maps, depth_radius=args.depth_radius, densify=getattr(args, "densify", 0),
+                              mesh=getattr(args, "mesh", 0))
         return
     if getattr(args, "seeds", None):
         global_set = mvs.SeedSet.load(args.seeds)
@@ -116,7 +120,13 @@ if __name__ == "__main__":
     parser.add_argument("-densify", dest="densify", default=0, type=int,
                         help="--warped -depth_maps: densify the maps by this many sweeps of per-pixel plane "
                              "propagation (the default schedule: 1..12, anything above is refused; 0: none); needs -depth_maps")
+    parser.add_argument("-mesh", dest="mesh", default=0, type=int,
+                        help="--warped -depth_maps: fuse the maps into a signed-distance lattice of this many voxels "
+                             "along its longest side and write the surface as warped_mesh.ply (0: none); needs "
+                             "-depth_maps")
     args = parser.parse_args()
+    if args.mesh < 0 or (args.mesh > 0 and not (args.warped and args.depth_maps)):
+        parser.error("-mesh N needs N >= 0, --warped and -depth_maps DIR")
     try:
         main(args)
     except RuntimeError as e:

@@ -17,7 +17,7 @@ import zlib
 import numpy as np
 
 from . import _lib
-from .utils import export2ply, export2ply_oriented, pars_to_arrays, read_pars, tracks_to_arrays
+from .utils import export2ply, export2ply_mesh, export2ply_oriented, pars_to_arrays, read_pars, tracks_to_arrays
 
 last_stats = {}
 _ctx_cache = {}
@@ -172,6 +172,13 @@ def densify_depth_warped(ctx, maps, **kw):
     return ctx.densify_depth(maps, **kw)
 
 
+def mesh_depth_warped(ctx, maps, **kw):
+    """A triangle mesh of the maps of depth_maps_warped or densify_depth_warped:
+    signed-distance fusion and marching tetrahedra (no reference counterpart;
+    see MvsContext.mesh_depth, which takes the keywords): `maps` needs z."""
+    return ctx.mesh_depth(maps, **kw)
+
+
 def write_depth_maps(maps, directory, first_view=0, dense_path="warped_dense"):
     """The files of a depth_maps_warped or densify_depth_warped result:
     directory/depth_%04d.npy (H,W) float32, nan for empty pixels, and
@@ -190,7 +197,7 @@ def write_depth_maps(maps, directory, first_view=0, dense_path="warped_dense"):
 
 def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1e-4, neighbours=4, min_axis_cos=0.5,
                       feats=None, pairs=None, path="warped_patches", device=None, depth_maps=None, depth_radius=1,
-                      dense_path="warped_dense", densify=0, **kw):
+                      dense_path="warped_dense", densify=0, mesh=0, mesh_path="warped_mesh", **kw):
     """An oriented, coloured point cloud from calibrated images alone (no
     reference counterpart; PMVS's match -> expand -> filter on the warped
     pipeline, without SfM tracks):
@@ -218,7 +225,12 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
     densified maps are written instead, with score_%04d.npy per view, the dense
     cloud is fused from them, and the count line and the counts gain
     "densified", the pixels that hold a depth afterwards.  N above the schedule's
-    12 sweeps, or N > 0 without depth_maps, raises RuntimeError.
+    12 sweeps, or N > 0 without depth_maps, raises RuntimeError.  mesh = N > 0
+    (default 0: nothing changes): MvsContext.mesh_depth of those maps (densified
+    when densify is given) at resolution N, written by export2ply_mesh as
+    mesh_path + '.ply'; the count line and the counts gain "mesh_vertices" and
+    "mesh_faces" and the returned dict gains "mesh".  N > 0 without depth_maps
+    raises RuntimeError.
 
     Returns a dict: points, normals, colors (n,3), nviews, patches (the final
     set as reconstruct_warped returns it) and counts (features, pairs, tests,
@@ -230,6 +242,11 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
         raise RuntimeError(f"densify must be in 0..{len(_lib.MvsContext.DENSIFY_SCHEDULE)} (the sweeps of the default schedule)")
     if densify > 0 and depth_maps is None:
         raise RuntimeError("densify needs depth_maps (a directory for the maps it densifies)")
+    mesh = int(mesh)
+    if mesh < 0:
+        raise RuntimeError("mesh must be >= 0 (the lattice's resolution along the longest side)")
+    if mesh > 0 and depth_maps is None:
+        raise RuntimeError("mesh needs depth_maps (a directory for the maps it fuses)")
     par_K, par_r, par_t = read_pars(args)
     ctx = scene_context(imgs, par_K, par_r, par_t, device)
     expand = dict(kw.pop("expand", None) or {})
@@ -246,7 +263,7 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
     counts["patches"] = [h["patches"] for h in ps["history"]] + [len(ps["ref"])]
     colors, nviews = ctx.wpatch_color(ps["c"], ps["ref"], ps["mask"])
     export2ply_oriented(ps["c"], ps["nrm"], colors, path=path)
-    maps = None
+    maps = surface = None
     if depth_maps is not None:
         maps = ctx.depth_maps(ps, radius=depth_radius)
         if densify > 0:
@@ -254,16 +271,23 @@ def DensePointsWarped(imgs, args, rounds=4, iterations=3, epi_px=1.5, min_sin2=1
             counts["densified"] = int(np.isfinite(maps["z"]).sum())
         write_depth_maps(maps, depth_maps, dense_path=dense_path)
         counts["dense"] = len(maps["points"])
+        if mesh > 0:
+            surface = ctx.mesh_depth(maps, resolution=mesh)
+            export2ply_mesh(surface["vertices"], surface["colors"], surface["faces"], path=mesh_path)
+            counts["mesh_vertices"], counts["mesh_faces"] = len(surface["vertices"]), len(surface["faces"])
     counts["seconds"] = time.time() - t0
     print("warped: features {features} pairs {pairs} candidates {candidates} round-0 winners {winners0} "
           "patches per iteration {patches}".format(**counts) + (" dense {dense}".format(**counts) if maps else "")
-          + (" densified {densified}".format(**counts) if "densified" in counts else ""))
+          + (" densified {densified}".format(**counts) if "densified" in counts else "")
+          + (" mesh vertices {mesh_vertices} faces {mesh_faces}".format(**counts) if surface is not None else ""))
     last_stats.clear()
     last_stats.update(counts)
     out = {"points": ps["c"], "normals": ps["nrm"], "colors": colors, "nviews": nviews, "patches": ps,
            "counts": counts}
     if maps is not None:
         out["maps"] = maps
+    if surface is not None:
+        out["mesh"] = surface
     return out
 
 

@@ -16,7 +16,8 @@ ASAN_LIB = os.path.join(HERE, "libmvs_amd_asan.so")       # host code under ASan
 # the one list of sources (tools/build_variant.sh reads it through --sources), the slowest to compile first
 SOURCES = ["mvs_score_tab.hip", "mvs_score_mma.hip", "mvs_score_mma_v.hip", "mvs_sort.hip", "mvs_kernels.hip",
            "mvs_bin.hip", "mvs_exchange.hip", "mvs_warp.hip", "mvs_refine.hip", "mvs_expand_warp.hip", "mvs_filter_warp.hip",
-           "mvs_seed_warp.hip", "mvs_depth_warp.hip", "mvs_prop_warp.hip", "sfm_kernels.hip", "mvs_engine.cpp", "mvs_context.cpp", "mvs_warped.cpp", "mvs_geometry.cpp"]
+           "mvs_seed_warp.hip", "mvs_depth_warp.hip", "mvs_prop_warp.hip", "mvs_mesh_warp.hip",
+           "sfm_kernels.hip", "mvs_engine.cpp", "mvs_context.cpp", "mvs_warped.cpp", "mvs_geometry.cpp"]
 
 # every header a source may include, found, not listed: csrc/*.h and the public header (paths from csrc/)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "mvs_amd.h")]

@@ -238,13 +238,15 @@ void mvs_ctx_destroy(mvs_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     // the scratch's last users may be any streams (some perhaps destroyed by now)
-    if (ctx->scratch_order.used || ctx->pack_order.used || ctx->wexp_order.used) (void)hipDeviceSynchronize();
+    if (ctx->scratch_order.used || ctx->pack_order.used || ctx->wexp_order.used || ctx->wmesh_order.used)
+        (void)hipDeviceSynchronize();
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->scratch_order.ev) (void)hipEventDestroy(ctx->scratch_order.ev);
     if (ctx->pack_order.ev) (void)hipEventDestroy(ctx->pack_order.ev);
     if (ctx->wexp_order.ev) (void)hipEventDestroy(ctx->wexp_order.ev);
+    if (ctx->wmesh_order.ev) (void)hipEventDestroy(ctx->wmesh_order.ev);
     delete ctx;
 }
 
@@ -423,6 +425,7 @@ int mvs_stream_retiring(mvs_ctx* ctx, void* stream) {
         ctx->scratch_order.retire((hipStream_t)stream);
         ctx->pack_order.retire((hipStream_t)stream);
         ctx->wexp_order.retire((hipStream_t)stream);
+        ctx->wmesh_order.retire((hipStream_t)stream);
         return 0;
     });
 }

@@ -214,6 +214,12 @@ struct mvs_ctx {
     // x_cnt, x_offs and wexp_order with the expansion)
     PinnedTable s_tab_h;
     DevBuf<unsigned char> s_tab;
+    // the mesh extraction's scratch (mvs_wmesh_extract, ordered by wmesh_order):
+    // the points' used-edge masks and first vertices, the workgroups' vertex and
+    // triangle counts
+    DevBuf<uint32_t> m_mask;
+    DevBuf<int32_t> m_voff;
+    DevBuf<int64_t> m_sums;
     // tiled scorer scratch
     DevBuf<int32_t> t_tiles, t_cand;
     // mvs_pack_accepted: the pack's row counter and chunk ticket (k_acc_pack
@@ -341,7 +347,7 @@ struct mvs_ctx {
             used = false;
             s = nullptr;
         }
-    } scratch_order, pack_order, wexp_order;
+    } scratch_order, pack_order, wexp_order, wmesh_order;
     std::string err;
     void scratch_acquire(hipStream_t s) { scratch_order.acquire(s); }
     void scratch_release(hipStream_t s) { scratch_order.release(s); }

@@ -275,6 +275,41 @@ struct WpropArgs {
     double* scores;         // H*W*HY (may be null), HY = 5 + (2 kd + 1)(2 ka + 1)^2
 };
 
+// The signed-distance lattice of the depth maps (mvs_mesh_warp.hip; device
+// pointers).  (nx+1)(ny+1)(nz+1) points, point (i, j, k) at linear index
+// (k (ny+1) + j)(nx+1) + i; every output is written whole.
+struct WtsdfArgs {
+    const double* zmap;     // nv*H*W
+    int v0, nv;
+    int nx, ny, nz;
+    double origin[3], voxel, trunc;
+    int min_weight;
+    double* tsdf;           // points
+    int32_t* weight;        // points
+    uint8_t* rgb;           // points*3
+    uint8_t* cnt;           // points
+};
+// Marching tetrahedra over such a lattice.  Workgroups of MVS_MESH_BLOCK
+// threads; cube (i, j, k) at linear index (k ny + j) nx + i.
+#define MVS_MESH_BLOCK 256
+struct WmeshArgs {
+    int nx, ny, nz;
+    double origin[3], voxel;
+    const double* tsdf;     // points
+    const uint8_t* rgb;     // points*3
+    const uint8_t* cnt;     // points
+    int64_t cap_v, cap_t;
+    double* vert;           // cap_v*3
+    uint8_t* vcol;          // cap_v*3
+    int32_t* tri;           // cap_t*3
+    int64_t* total;         // 2: vertices, triangles
+    // scratch (the context's, ordered by wmesh_order)
+    uint32_t* mask;         // ceil(points / 4) words, zero on entry: the used-edge bits, a byte per point
+    int32_t* voff;          // points: a point's first vertex
+    int64_t* tsum;          // cube workgroups + 1: their triangle counts, then the exclusive offsets
+    int64_t* vsum;          // point workgroups + 1: likewise for vertices
+};
+
 // Scratch of the tiled scorer (device pointers, sized by the host).
 //   tile_count[k * MVS_TC_STRIDE]: tile k's count (stride 1: a wave's atomics
 //   on 64 neighbouring tiles share two cache lines -- measured 20 us faster
@@ -486,6 +521,11 @@ int mvs_launch_wdepth_points(const SceneDev* sc, const WpointsArgs* a, hipStream
 // one view of a propagation sweep (k_wprop_sweep, mvs_prop_warp.hip): a wave per
 // 16 pixels, lane = (hypothesis, list view); wid in 1..5
 int mvs_launch_wprop_sweep(const SceneDev* sc, const WpropArgs* a, int wid, hipStream_t s);
+// the fusion and the mesh (mvs_mesh_warp.hip): integrate = k_wtsdf_integrate;
+// extract = k_wmesh_mark, k_wmesh_vcount, k_wmesh_scan, then k_wmesh_vertex and
+// k_wmesh_tri (neither when both caps are 0)
+int mvs_launch_wtsdf_integrate(const SceneDev* sc, const WtsdfArgs* a, hipStream_t s);
+int mvs_launch_wmesh_extract(const WmeshArgs* a, hipStream_t s);
 // tiled scorer (mvs_bin.hip): k_bin (tile buckets, then the work items), the
 // scorer of the scene's shape through its launcher below (timed by ev0/ev1),
 // k_score_fix

@@ -1149,4 +1149,186 @@ int mvs_wprop_sweep(mvs_ctx* ctx, int v0, int nv, const double* zmap, const doub
     });
 }
 
+// ---- the signed-distance lattice and its mesh (mvs_mesh_warp.hip) ----
+
+// the lattice's checks; *points = the number of lattice points.  0, or the error's code
+static int lattice_check(mvs_ctx* ctx, const char* who, int nx, int ny, int nz, const double* origin, double voxel,
+                         int64_t* points) {
+    if (nx < 1 || ny < 1 || nz < 1) return bad_arg(ctx, who, "nx, ny and nz must be >= 1");
+    const int64_t limit = (int64_t)1 << 27;
+    // factor by factor: the product of three ints can pass 2^63
+    if (nx >= limit || ny >= limit || nz >= limit || ((int64_t)nx + 1) * ((int64_t)ny + 1) > limit ||
+        ((int64_t)nx + 1) * ((int64_t)ny + 1) * ((int64_t)nz + 1) > limit)
+        return bad_arg(ctx, who, "more than 2^27 lattice points");
+    if (!origin) return bad_arg(ctx, who, "null pointer (origin)");
+    for (int m = 0; m < 3; ++m)
+        if (!std::isfinite(origin[m])) return bad_arg(ctx, who, "origin must be finite");
+    if (!(voxel > 0.0 && voxel < HUGE_VAL)) return bad_arg(ctx, who, "voxel must be finite and > 0");
+    *points = ((int64_t)nx + 1) * ((int64_t)ny + 1) * ((int64_t)nz + 1);
+    return 0;
+}
+
+static int wtsdf_check(mvs_ctx* ctx, int v0, int nv, int nx, int ny, int nz, const double* origin, double voxel,
+                       double trunc, int min_weight, bool ptrs_ok, int64_t* points) {
+    const char* who = "mvs_wtsdf_integrate";
+    if (int rc = lattice_check(ctx, who, nx, ny, nz, origin, voxel, points)) return rc;
+    if (!(trunc > 0.0 && trunc < HUGE_VAL)) return bad_arg(ctx, who, "trunc must be finite and > 0");
+    if (min_weight < 1) return bad_arg(ctx, who, "min_weight must be >= 1");
+    if (int rc = need_views(ctx, who, v0, nv)) return rc;
+    if (!ptrs_ok) return bad_arg(ctx, who, "null pointer");
+    return 0;
+}
+
+static void wtsdf_launch(mvs_ctx* ctx, const double* d_zmap, int v0, int nv, int nx, int ny, int nz,
+                         const double* origin, double voxel, double trunc, int min_weight, double* d_tsdf,
+                         int32_t* d_weight, uint8_t* d_rgb, uint8_t* d_cnt, hipStream_t s) {
+    WtsdfArgs a{};
+    a.zmap = d_zmap;
+    a.v0 = v0;
+    a.nv = nv;
+    a.nx = nx;
+    a.ny = ny;
+    a.nz = nz;
+    for (int m = 0; m < 3; ++m) a.origin[m] = origin[m];
+    a.voxel = voxel;
+    a.trunc = trunc;
+    a.min_weight = min_weight;
+    a.tsdf = d_tsdf;
+    a.weight = d_weight;
+    a.rgb = d_rgb;
+    a.cnt = d_cnt;
+    if (mvs_launch_wtsdf_integrate(&ctx->sc, &a, s) != 0) throw Fail{MVS_E_HIP, "wtsdf_integrate launch failed"};
+}
+
+int mvs_wtsdf_integrate_device(mvs_ctx* ctx, const double* d_zmap, int v0, int nv, int nx, int ny, int nz,
+                               const double* origin, double voxel, double trunc, int min_weight, double* d_tsdf,
+                               int32_t* d_weight, uint8_t* d_rgb, uint8_t* d_cnt, void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    int64_t points = 0;
+    if (int rc = wtsdf_check(ctx, v0, nv, nx, ny, nz, origin, voxel, trunc, min_weight,
+                             d_zmap && d_tsdf && d_weight && d_rgb && d_cnt, &points))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wtsdf_launch(ctx, d_zmap, v0, nv, nx, ny, nz, origin, voxel, trunc, min_weight, d_tsdf, d_weight, d_rgb,
+                     d_cnt, s);
+        return 0;
+    });
+}
+
+int mvs_wtsdf_integrate(mvs_ctx* ctx, const double* zmap, int v0, int nv, int nx, int ny, int nz,
+                        const double* origin, double voxel, double trunc, int min_weight, double* tsdf,
+                        int32_t* weight, uint8_t* rgb, uint8_t* cnt) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    int64_t points = 0;
+    if (int rc = wtsdf_check(ctx, v0, nv, nx, ny, nz, origin, voxel, trunc, min_weight,
+                             zmap && tsdf && weight && rgb && cnt, &points))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_zmap = st.in(zmap, (int64_t)nv * ctx->H * ctx->W);
+        const auto d_tsdf = st.out(tsdf, points);
+        const auto d_weight = st.out(weight, points);
+        const auto d_rgb = st.out(rgb, points * 3);
+        const auto d_cnt = st.out(cnt, points);
+        st.upload();
+        wtsdf_launch(ctx, d_zmap, v0, nv, nx, ny, nz, origin, voxel, trunc, min_weight, d_tsdf, d_weight, d_rgb,
+                     d_cnt, s);
+        st.finish();
+        return 0;
+    });
+}
+
+static int wmesh_check(mvs_ctx* ctx, int nx, int ny, int nz, const double* origin, double voxel, int64_t cap_v,
+                       int64_t cap_t, bool in_ok, bool vert_ok, bool tri_ok, int64_t* points) {
+    const char* who = "mvs_wmesh_extract";
+    if (int rc = lattice_check(ctx, who, nx, ny, nz, origin, voxel, points)) return rc;
+    if (int rc = need_nonneg(ctx, who, "cap_v", cap_v)) return rc;
+    if (int rc = need_nonneg(ctx, who, "cap_t", cap_t)) return rc;
+    if (cap_v >= ((int64_t)1 << 31) || cap_t >= ((int64_t)1 << 31))
+        return bad_arg(ctx, who, "cap_v and cap_t must be below 2^31");
+    if (!in_ok || (cap_v > 0 && !vert_ok) || (cap_t > 0 && !tri_ok))
+        return bad_arg(ctx, who, "null pointer (vert and vcol may be NULL when cap_v is 0, tri when cap_t is 0)");
+    return 0;
+}
+
+static void wmesh_launch(mvs_ctx* ctx, int nx, int ny, int nz, const double* origin, double voxel,
+                         const double* d_tsdf, const uint8_t* d_rgb, const uint8_t* d_cnt, int64_t cap_v,
+                         int64_t cap_t, double* d_vert, uint8_t* d_vcol, int32_t* d_tri, int64_t* d_total,
+                         hipStream_t s) {
+    const int64_t points = ((int64_t)nx + 1) * (ny + 1) * (nz + 1), cubes = (int64_t)nx * ny * nz;
+    const int64_t nbv = (points + MVS_MESH_BLOCK - 1) / MVS_MESH_BLOCK;
+    const int64_t nbt = (cubes + MVS_MESH_BLOCK - 1) / MVS_MESH_BLOCK;
+    ctx->wmesh_order.acquire(s);
+    ctx->m_mask.ensure((size_t)((points + 3) / 4));
+    ctx->m_voff.ensure((size_t)points);
+    ctx->m_sums.ensure((size_t)(nbv + nbt + 2));
+    WmeshArgs a{};
+    a.nx = nx;
+    a.ny = ny;
+    a.nz = nz;
+    for (int m = 0; m < 3; ++m) a.origin[m] = origin[m];
+    a.voxel = voxel;
+    a.tsdf = d_tsdf;
+    a.rgb = d_rgb;
+    a.cnt = d_cnt;
+    a.cap_v = cap_v;
+    a.cap_t = cap_t;
+    a.vert = d_vert;
+    a.vcol = d_vcol;
+    a.tri = d_tri;
+    a.total = d_total;
+    a.mask = ctx->m_mask.p;
+    a.voff = ctx->m_voff.p;
+    a.vsum = ctx->m_sums.p;
+    a.tsum = ctx->m_sums.p + nbv + 1;
+    // s uses the scratch from here on, also when a later pass fails to launch after earlier ones were queued
+    ctx->wmesh_order.release(s);
+    if (mvs_launch_wmesh_extract(&a, s) != 0) throw Fail{MVS_E_HIP, "wmesh_extract launch failed"};
+}
+
+int mvs_wmesh_extract_device(mvs_ctx* ctx, int nx, int ny, int nz, const double* origin, double voxel,
+                             const double* d_tsdf, const uint8_t* d_rgb, const uint8_t* d_cnt, int64_t cap_v,
+                             int64_t cap_t, double* d_vert, uint8_t* d_vcol, int32_t* d_tri, int64_t* d_total,
+                             void* stream) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    int64_t points = 0;
+    if (int rc = wmesh_check(ctx, nx, ny, nz, origin, voxel, cap_v, cap_t, d_tsdf && d_rgb && d_cnt && d_total,
+                             d_vert && d_vcol, d_tri != nullptr, &points))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+        wmesh_launch(ctx, nx, ny, nz, origin, voxel, d_tsdf, d_rgb, d_cnt, cap_v, cap_t, d_vert, d_vcol, d_tri,
+                     d_total, s);
+        return 0;
+    });
+}
+
+int mvs_wmesh_extract(mvs_ctx* ctx, int nx, int ny, int nz, const double* origin, double voxel, const double* tsdf,
+                      const uint8_t* rgb, const uint8_t* cnt, int64_t cap_v, int64_t cap_t, double* vert,
+                      uint8_t* vcol, int32_t* tri, int64_t* total) {
+    if (!ctx) return set_err(nullptr, Fail{MVS_E_ARG, "null context"});
+    int64_t points = 0;
+    if (int rc = wmesh_check(ctx, nx, ny, nz, origin, voxel, cap_v, cap_t, tsdf && rgb && cnt && total, vert && vcol,
+                             tri != nullptr, &points))
+        return rc;
+    return guarded(ctx, [&]() {
+        hipStream_t s = ctx->stream;
+        Staging& st = ctx->staging.begin(s);
+        const auto d_tsdf = st.in(tsdf, points);
+        const auto d_rgb = st.in(rgb, points * 3);
+        const auto d_cnt = st.in(cnt, points);
+        const auto d_vert = st.out(cap_v ? vert : nullptr, cap_v * 3);
+        const auto d_vcol = st.out(cap_v ? vcol : nullptr, cap_v * 3);
+        const auto d_tri = st.out(cap_t ? tri : nullptr, cap_t * 3);
+        const auto d_total = st.out(total, 2);
+        st.upload();
+        wmesh_launch(ctx, nx, ny, nz, origin, voxel, d_tsdf, d_rgb, d_cnt, cap_v, cap_t, d_vert, d_vcol, d_tri,
+                     d_total, s);
+        st.finish();
+        return 0;
+    });
+}
+
 }  // extern "C"

@@ -102,6 +102,61 @@ def read_ply_oriented(path):
     return rows[:, :3], rows[:, 3:6], rows[:, 6:]
 
 
+_MESH_VERTEX = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_MESH_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def export2ply_mesh(vertices, colors, faces, path="output"):
+    """Write path + '.ply' (binary little-endian): a triangle mesh with double
+    x y z and uchar red green blue per vertex and a face list of int32 indices."""
+    vert = np.asarray(vertices, np.float64).reshape(-1, 3)
+    col = np.asarray(colors, np.uint8).reshape(-1, 3)
+    tri = np.asarray(faces, np.int32).reshape(-1, 3)
+    if len(vert) != len(col):
+        raise RuntimeError("export2ply_mesh: vertices and colors differ in length")
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(vert)):
+        raise RuntimeError("export2ply_mesh: a face names a vertex that does not exist")
+    v = np.empty(len(vert), _MESH_VERTEX)
+    for k, name in enumerate(("x", "y", "z")):
+        v[name] = vert[:, k]
+    for k, name in enumerate(("red", "green", "blue")):
+        v[name] = col[:, k]
+    f = np.empty(len(tri), _MESH_FACE)
+    f["n"] = 3
+    f["v"] = tri
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\n"
+              "property double x\nproperty double y\nproperty double z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+              f"element face {len(f)}\n"
+              "property list uchar int vertex_indices\n"
+              "end_header\n")
+    with open(path + ".ply", "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+
+
+def read_ply_mesh(path):
+    """Inverse of export2ply_mesh: vertices (n, 3) float64, colors (n, 3) uint8, faces (m, 3) int32."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode().splitlines()
+    props = [ln.split()[1:] for ln in head if ln.startswith("property")]
+    want = [["double", p] for p in ("x", "y", "z")] + [["uchar", p] for p in ("red", "green", "blue")]
+    if props != want + [["list", "uchar", "int", "vertex_indices"]]:
+        raise RuntimeError(f"{path}: not a mesh of export2ply_mesh")
+    n = int([ln for ln in head if ln.startswith("element vertex")][0].split()[-1])
+    m = int([ln for ln in head if ln.startswith("element face")][0].split()[-1])
+    v = np.frombuffer(raw, _MESH_VERTEX, count=n, offset=end)
+    f = np.frombuffer(raw, _MESH_FACE, count=m, offset=end + n * _MESH_VERTEX.itemsize)
+    if len(f) and (f["n"] != 3).any():
+        raise RuntimeError(f"{path}: a face is not a triangle")
+    return (np.stack([v["x"], v["y"], v["z"]], 1).reshape(n, 3), np.stack([v["red"], v["green"], v["blue"]], 1).reshape(n, 3),
+            f["v"].astype(np.int32).reshape(m, 3))
+
+
 def tracks_to_arrays(tracks):
     """[track.point2d_list = [(view, x, y), ...]] -> (track_off i64, obs_view i32, obs_xy f32)."""
     off, view, xy = [0], [], []
